@@ -7,6 +7,11 @@ One step = full calibration of one solution interval (tile):
   refinement -> per-channel residual computation.
 
 Run:  python bench.py [--gpus N] [--steps K] [--warmup W]
+                      [--dump-outputs DIR] [--full]
+A plain run only sets up, warms up, times the K steps and prints the
+result line. --dump-outputs DIR also writes what the last timed step
+computed as DIR/<name>.npy; --full enables the secondary measurements
+(the headline run has none of its own today).
 Multi-GPU (driver): torchrun --nproc-per-node N bench.py --gpus N ...
   each rank calibrates its own frequency sub-band (the sagecal-mpi
   frequency-parallel decomposition) coupled by consensus-ADMM polynomial
@@ -66,19 +71,24 @@ def build_problem(args, device, dtype, rank=0, world=1):
     pack = SourcePack(clusters)
     # per-rank frequency sub-band (sagecal-mpi: one MS band per worker)
     freq0 = args.freq0 + rank * args.bandwidth
-    # synthetic truth is generated in fp64; for large arrays generate on
-    # the GPU (fp64 on device) — CPU generation at 512 stations takes
-    # minutes and starves the bench setup
+    # synthetic truth is generated in fp64 on the device the run uses:
+    # CPU generation takes ~2 min at the headline shape (1.94 M rows) and
+    # longer at 512 stations, which starves the bench setup. The noise
+    # comes from the seeded numpy generator either way. Large arrays
+    # keep the sky model resident on the GPU as before; smaller ones
+    # generate from a device copy and solve from the host-side pack.
     nb_rows = nb * args.tilesz * P
-    gen_dev = device if (device != 'cpu' and nb_rows >= 2**21) else 'cpu'
-    if gen_dev != 'cpu':
-        pack.to(gen_dev)
+    gen_pack = pack
+    if device != 'cpu':
+        if nb_rows < 2**21:
+            gen_pack = SourcePack(clusters)
+        gen_pack.to(device)
     ms = msdata.SyntheticMS(
         N=args.stations, tilesz=args.tilesz * P, Ntime=args.tilesz * P,
         Nchan=args.chan, freq0=freq0, bandwidth=args.bandwidth,
-        tdelta=10.0, pack=pack, seed=101 + rank,
+        tdelta=10.0, pack=gen_pack, seed=101 + rank,
         noise_sigma=5e-3, robust_noise=4.0,
-        device=gen_dev, dtype=torch.float64)
+        device=device, dtype=torch.float64)
     tile = ms.load_tile(0)
     if device != 'cpu':
         cdt = torch.complex64 if dtype == torch.float32 else torch.complex128
@@ -90,6 +100,36 @@ def build_problem(args, device, dtype, rank=0, world=1):
         tile.flags = tile.flags.to(device)
     bb = ms.bb_tensor(device=device)
     return pack, ms, tile, bb
+
+
+DUMP_BUDGET = 48 * 2**20     # bytes over all arrays (limit: 64 MB)
+
+
+def dump_outputs(dirname, arrays, rank=0):
+    """Write each named tensor as DIR/<name>.npy in float32/float64
+    (complex gets a trailing re/im axis). An array larger than its share
+    of DUMP_BUDGET is reduced to a fixed, seeded sample of its flattened
+    elements, so two builds dump the same entries."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        if not (t.is_floating_point() or t.is_complex()):
+            t = t.to(torch.float64)
+        if t.dtype in (torch.float16, torch.bfloat16):
+            t = t.to(torch.float32)
+        elif t.dtype == torch.complex32:
+            t = t.to(torch.complex64)
+        if t.numel() * t.element_size() > share:
+            k = share // t.element_size()
+            idx = np.sort(np.random.default_rng(2024).integers(
+                0, t.numel(), size=k))
+            t = t.reshape(-1)[torch.as_tensor(idx, device=t.device)]
+        if t.is_complex():
+            t = torch.view_as_real(t.resolve_conj())
+        fn = name if rank == 0 else f'{name}.rank{rank}'
+        np.save(os.path.join(dirname, fn + '.npy'),
+                t.cpu().contiguous().numpy())
 
 
 def run_step(state, pack, tile, bb, opts, args, device, adm=None):
@@ -149,7 +189,7 @@ def run_bandpass(args, device, dtype, rank, world):
         multifreq=not args.band_average)
     def step():
         cal.epoch(tile, bb, nmb=2, lbfgs_iters=6, robust_nu=10.0)
-    return step, tile
+    return step, tile, cal
 
 
 def main():
@@ -192,6 +232,14 @@ def main():
     ap.add_argument('--admm-rho', type=float, default=5.0)
     ap.add_argument('--no-consensus', action='store_true')
     ap.add_argument('--cpu', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last '
+                         'timed step computed as DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='reserved for secondary measurements; the '
+                         'benchmark has none today, so this changes '
+                         'nothing (a plain run does only setup, warmup, '
+                         'the timed steps and the result line)')
     args = ap.parse_args()
 
     rank = int(os.environ.get('RANK', '0'))
@@ -222,7 +270,7 @@ def main():
     from sagecal_amd.constants import SM_RLM_RLBFGS, SM_RTR_OSRLM_RLBFGS
 
     if args.mode == 'bandpass':
-        stepfn, tile = run_bandpass(args, device, dtype, rank, world)
+        stepfn, tile, cal = run_bandpass(args, device, dtype, rank, world)
 
         def sync():
             if use_gpu:
@@ -243,6 +291,10 @@ def main():
             torch.distributed.all_reduce(
                 te, op=torch.distributed.ReduceOp.MAX)
             elapsed = float(te)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {
+                'band_jones': torch.stack([st.J for st in cal.states]),
+                'consensus_z': cal.Z}, rank)
         Nbase = args.stations * (args.stations - 1) // 2
         vis_per_step = Nbase * args.tilesz * args.chan
         if rank == 0:
@@ -308,6 +360,12 @@ def main():
         te = torch.tensor([elapsed], device=device if use_gpu else 'cpu')
         torch.distributed.all_reduce(te, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(te)
+    if args.dump_outputs and res is not None:
+        dump_outputs(args.dump_outputs, {
+            'res': torch.tensor([float(res[0]), float(res[1])],
+                                dtype=torch.float64),
+            'residuals': res[2],
+            'jones': state.J}, rank)
 
     Nbase = args.stations * (args.stations - 1) // 2
     vis_per_step = Nbase * args.tilesz * args.intervals * args.chan

@@ -186,8 +186,6 @@ def _run_multiplexed(args, names, rank, world, device, dtype, cdtype):
             print(f"rank {rank} tile {ti_all}: bands {rr}")
     for ms in mss:
         ms.save()
-    if world > 1:
-        dist.destroy_process_group()
     return 0
 
 
@@ -224,8 +222,6 @@ def _run_federated_stochastic(args, ms, pack, device, cdtype, rank,
                   f"epochs {args.epochs}, "
                   f"res {float(xres.abs().pow(2).mean()):.6f}")
     ms.save()
-    if world > 1 and dist.is_initialized():
-        dist.destroy_process_group()
     return 0
 
 
@@ -268,12 +264,26 @@ def _diffuse_hook(args, pack, tile, bb):
 
 def main(argv=None):
     args = build_argparser().parse_args(argv)
+    world = int(os.environ.get('WORLD_SIZE', '1'))
+    # a process group the caller set up is the caller's to tear down:
+    # destroying it here and re-creating it on the next call races with
+    # slower ranks that still serve the old rendezvous store
+    own_pg = world > 1 and not dist.is_initialized()
+    if own_pg:
+        dist.init_process_group(
+            'nccl' if torch.cuda.is_available() else 'gloo')
+    try:
+        return _main(args)
+    finally:
+        if own_pg and dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def _main(args):
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', str(rank)))
     use_gpu = torch.cuda.is_available()
-    if world > 1 and not dist.is_initialized():
-        dist.init_process_group('nccl' if use_gpu else 'gloo')
     if use_gpu:
         torch.cuda.set_device(local_rank)
     device = f'cuda:{local_rank}' if use_gpu else 'cpu'
@@ -493,8 +503,6 @@ def main(argv=None):
                     fh.write(str(p) + ''.join(
                         f" {v.real:e} {v.imag:e}" for v in
                         Zsp[p].tolist()) + "\n")
-    if world > 1:
-        dist.destroy_process_group()
     return 0
 
 

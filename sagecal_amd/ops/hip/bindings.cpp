@@ -13,13 +13,14 @@ hipError_t launch_predict_coh(const double*, const double*, const double*,
     double, const float*, const int*, int, int, int, float2*,
     hipStream_t);
 hipError_t launch_jtj_accum(const float2*, const float2*, const float2*,
-    const int*, const int*, const float*, int, int, int, int, float2*,
-    float2*, float2*, float*, int, int, hipStream_t);
+    const int*, const int*, const int*, const float*, int, int, int, int,
+    int, float2*, float2*, float*, int*, float2*, float2*, float2*, float*,
+    int, int, hipStream_t);
 hipError_t launch_jtj_expand(const float2*, const float2*, const float2*,
     const int*, int, int, int, float*, float*, hipStream_t);
 hipError_t launch_model_cost(const float2*, const float2*, const float2*,
-    const int*, const int*, const float*, int, int, int, int, float*,
-    hipStream_t);
+    const int*, const int*, const float*, int, int, int, int, int, float*,
+    float*, hipStream_t);
 hipError_t launch_apply_jones(const float2*, const float2*, const float2*,
     const int*, const int*, int, int, int, int, int, int, float2*,
     hipStream_t);
@@ -94,10 +95,19 @@ std::vector<torch::Tensor> jtj_jtr(
   auto g = torch::zeros({Mt * N, 4}, copts);
   auto Cx = torch::zeros({Mt * npair, 16}, copts);
   auto cost = torch::zeros({Mt}, fopts);
+  // per-(chunk, pair) partial slots of the store pass; only slots of
+  // chunks marked present are read back
+  auto PD = torch::empty({Mt * npair, 8}, copts);
+  auto Pg = torch::empty({Mt * npair, 8}, copts);
+  auto Pc = torch::empty({Mt * npair}, fopts);
+  auto present = torch::zeros({Mt},
+      torch::dtype(torch::kInt).device(x.device()));
   const float* wp = wts.has_value() ? wts->data_ptr<float>() : nullptr;
   CHECK_HIP(launch_jtj_accum(ccptr(x), ccptr(coh), ccptr(J),
-      pairs.data_ptr<int>(), chunk_tab.data_ptr<int>(), wp,
-      (int)Nbase, (int)T, (int)N, (int)nseg, cptr(D), cptr(g), cptr(Cx),
+      pairs.data_ptr<int>(), chunk_tab.data_ptr<int>(),
+      pidx.data_ptr<int>(), wp, (int)Nbase, (int)T, (int)N, (int)nseg,
+      (int)Mt, cptr(PD), cptr(Pg), Pc.data_ptr<float>(),
+      present.data_ptr<int>(), cptr(D), cptr(g), cptr(Cx),
       cost.data_ptr<float>(), (int)npair, 0, cur_stream()));
   auto JtJ = torch::empty({Mt, 8 * N, 8 * N}, fopts);
   auto Jtr = torch::empty({Mt, 8 * N}, fopts);
@@ -112,13 +122,15 @@ torch::Tensor model_cost(
     torch::Tensor pairs, torch::Tensor chunk_tab,
     c10::optional<torch::Tensor> wts, int64_t Nbase, int64_t T, int64_t N,
     int64_t nseg, int64_t Mt) {
-  auto cost = torch::zeros({Mt},
-      torch::dtype(torch::kFloat).device(x.device()));
+  auto fopts = torch::dtype(torch::kFloat).device(x.device());
+  auto cost = torch::zeros({Mt}, fopts);
+  // per-row cost, then one sum per (seg, t) slot
+  auto e2 = torch::empty({nseg * T * Nbase + nseg * T}, fopts);
   const float* wp = wts.has_value() ? wts->data_ptr<float>() : nullptr;
   CHECK_HIP(launch_model_cost(ccptr(x), ccptr(coh), ccptr(J),
       pairs.data_ptr<int>(), chunk_tab.data_ptr<int>(), wp,
-      (int)Nbase, (int)T, (int)N, (int)nseg, cost.data_ptr<float>(),
-      cur_stream()));
+      (int)Nbase, (int)T, (int)N, (int)nseg, (int)Mt,
+      e2.data_ptr<float>(), cost.data_ptr<float>(), cur_stream()));
   return cost;
 }
 
@@ -171,7 +183,7 @@ std::vector<torch::Tensor> chol_solve_mw(
 
 std::vector<torch::Tensor> jtr_grad(
     torch::Tensor x, torch::Tensor coh, torch::Tensor J,
-    torch::Tensor pairs, torch::Tensor chunk_tab,
+    torch::Tensor pairs, torch::Tensor chunk_tab, torch::Tensor pidx,
     c10::optional<torch::Tensor> wts, int64_t Nbase, int64_t T, int64_t N,
     int64_t nseg, int64_t Mt) {
   // gradient-only accumulation (LBFGS path): returns (g [Mt*N,4] c64,
@@ -180,10 +192,16 @@ std::vector<torch::Tensor> jtr_grad(
   auto copts = torch::dtype(torch::kComplexFloat).device(x.device());
   auto g = torch::zeros({Mt * N, 4}, copts);
   auto cost = torch::zeros({Mt}, fopts);
+  auto Pg = torch::empty({Mt * Nbase, 8}, copts);
+  auto Pc = torch::empty({Mt * Nbase}, fopts);
+  auto present = torch::zeros({Mt},
+      torch::dtype(torch::kInt).device(x.device()));
   const float* wp = wts.has_value() ? wts->data_ptr<float>() : nullptr;
   CHECK_HIP(launch_jtj_accum(ccptr(x), ccptr(coh), ccptr(J),
-      pairs.data_ptr<int>(), chunk_tab.data_ptr<int>(), wp,
-      (int)Nbase, (int)T, (int)N, (int)nseg, nullptr, cptr(g), nullptr,
+      pairs.data_ptr<int>(), chunk_tab.data_ptr<int>(),
+      pidx.data_ptr<int>(), wp, (int)Nbase, (int)T, (int)N, (int)nseg,
+      (int)Mt, nullptr, cptr(Pg), Pc.data_ptr<float>(),
+      present.data_ptr<int>(), nullptr, cptr(g), nullptr,
       cost.data_ptr<float>(), (int)Nbase, 1, cur_stream()));
   return {g, cost};
 }

@@ -44,7 +44,3 @@ __device__ __forceinline__ void m2hmul(const cf* A, const cf* B, cf* C) {
   C[3] = cadd(cmulc(B[1], A[1]), cmulc(B[3], A[3]));
 }
 
-__device__ __forceinline__ void atomicAddCf(cf* dst, cf v) {
-  atomicAdd(&dst->x, v.x);
-  atomicAdd(&dst->y, v.y);
-}

@@ -6,8 +6,12 @@
 // (derivation in sagecal_amd/ops/reference.py jtj_jtr). One wave per
 // (station-pair, segment): lanes stride the time axis, accumulate complex
 // partials in registers, wave-reduce with 64-lane shuffles, then one lane
-// commits: per-station diagonal/gradient accumulators via atomics, the
-// unique per-(pair,chunk) cross block with plain stores.
+// commits everything with plain stores to its own (chunk, pair) slot: the
+// cross block, and the two stations' diagonal/gradient/cost partials.
+// k_jtj_reduce then sums each station's partials over its pairs in a fixed
+// order (store pass + per-destination sum pass), so the result is bitwise
+// reproducible from run to run — float atomics sum in arrival order, and
+// the LM accept/reject chain amplified that last-bit noise to 1e-3.
 //
 // Row layout contract (host-verified): rows = seg*(T*Nbase) + t*Nbase + b,
 // pair table pairs[b] = (p, q), chunk_tab[seg*T + t] = global chunk id.
@@ -20,11 +24,12 @@ __device__ __forceinline__ float wave_sum(float x) {
   return x;
 }
 
-// Accumulator layout:
-//  D   [Mt*N][4]  cf: diagonal 2x2 complex blocks (station side-sum)
-//  g   [Mt*N][4]  cf: per-station complex gradient
-//  Cx  [Mt*Npair][16] cf: cross block (i,j)x(k,b) complex entries
-//  cost[Mt] float
+// Per-(chunk, pair) slot layout (slot = c*npair_slots + b):
+//  Pg  [slots][8]  cf: gradient partials, station p side then q side
+//  PD  [slots][8]  cf: diagonal 2x2 block partials, p side then q side
+//  Pc  [slots]     float: cost partial
+//  Cx  [slots][16] cf: cross block (i,j)x(k,b) complex entries
+//  present[Mt] int: set for every chunk this launch covers
 extern "C" __global__ void __launch_bounds__(64)
 k_jtj_accum(const float2* __restrict__ x, const float2* __restrict__ coh,
             const float2* __restrict__ J,    // [Mt*N*4]
@@ -32,9 +37,9 @@ k_jtj_accum(const float2* __restrict__ x, const float2* __restrict__ coh,
             const int* __restrict__ chunk_tab,  // [nseg*T]
             const float* __restrict__ wts,   // [B] or nullptr
             int Nbase, int T, int N,
-            float2* __restrict__ D, float2* __restrict__ g,
-            float2* __restrict__ Cx, float* __restrict__ cost,
-            int npair_slots, int grad_only) {
+            float2* __restrict__ PD, float2* __restrict__ Pg,
+            float2* __restrict__ Cx, float* __restrict__ Pc,
+            int* __restrict__ present, int npair_slots, int grad_only) {
   const int b = blockIdx.x;        // pair index
   const int seg = blockIdx.y;
   const int lane = threadIdx.x;
@@ -122,28 +127,90 @@ k_jtj_accum(const float2* __restrict__ x, const float2* __restrict__ coh,
     }
     cst = wave_sum(cst);
     if (lane == 0) {
-      float2* Gp = g + ((size_t)c * N + p) * 4;
-      float2* Gq = g + ((size_t)c * N + q) * 4;
+      const size_t slot = (size_t)c * npair_slots + b;   // unique writer
+      float2* Gs = Pg + slot * 8;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        atomicAddCf(Gp + i, gp[i]);
-        atomicAddCf(Gq + i, gq[i]);
+        Gs[i] = gp[i];
+        Gs[4 + i] = gq[i];
       }
       if (!grad_only) {
-        float2* Dp = D + ((size_t)c * N + p) * 4;
-        float2* Dq = D + ((size_t)c * N + q) * 4;
+        float2* Ds = PD + slot * 8;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          atomicAddCf(Dp + i, Ap[i]);
-          atomicAddCf(Dq + i, Aq[i]);
+          Ds[i] = Ap[i];
+          Ds[4 + i] = Aq[i];
         }
-        float2* Xo = Cx + ((size_t)c * npair_slots + b) * 16;
+        float2* Xo = Cx + slot * 16;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) Xo[i] = Xc[i];   // unique writer
+        for (int i = 0; i < 16; ++i) Xo[i] = Xc[i];
       }
-      atomicAdd(&cost[c], cst);
+      Pc[slot] = cst;
+      present[c] = 1;      // same value from every writer
     }
     t0 = t1;
+  }
+}
+
+// Sum pass of k_jtj_accum's slots. Block (s, c), s < N: station s of
+// chunk c sums its side of every pair it belongs to (lane-strided over the
+// partner station, then the fixed 64-lane shuffle tree). Block (N, c):
+// the chunk's cost. Chunks the accumulate launch did not cover keep the
+// zeros the host put into D/g/cost.
+extern "C" __global__ void __launch_bounds__(64)
+k_jtj_reduce(const float2* __restrict__ PD, const float2* __restrict__ Pg,
+             const float* __restrict__ Pc, const int* __restrict__ present,
+             const int* __restrict__ pairs,  // [Nbase*2]
+             const int* __restrict__ pidx,   // [N*N] pair index or -1
+             int N, int Nbase, int npair_slots, int grad_only,
+             float2* __restrict__ D, float2* __restrict__ g,
+             float* __restrict__ cost) {
+  const int s = blockIdx.x;
+  const int c = blockIdx.y;
+  const int lane = threadIdx.x;
+  if (!present[c]) return;         // uniform over the block
+  const size_t slot0 = (size_t)c * npair_slots;
+  if (s == N) {
+    float cs = 0.f;
+    for (int b = lane; b < Nbase; b += WAVE) {
+      if (pairs[2 * b] >= 0 && pairs[2 * b + 1] >= 0) cs += Pc[slot0 + b];
+    }
+    cs = wave_sum(cs);
+    if (lane == 0) cost[c] = cs;
+    return;
+  }
+  cf sg[4] = {}, sd[4] = {};
+  for (int o = lane; o < N; o += WAVE) {
+    if (o == s) continue;
+    const int lo = o < s ? o : s, hi = o < s ? s : o;
+    const int pi = pidx[lo * N + hi];
+    if (pi < 0 || pi >= Nbase) continue;
+    int side;
+    if (pairs[2 * pi] == s) side = 0;
+    else if (pairs[2 * pi + 1] == s) side = 4;
+    else continue;                 // pair flagged in this layout
+    const float2* a = Pg + (slot0 + pi) * 8 + side;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sg[i] = cadd(sg[i], a[i]);
+    if (!grad_only) {
+      const float2* d = PD + (slot0 + pi) * 8 + side;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) sd[i] = cadd(sd[i], d[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    sg[i].x = wave_sum(sg[i].x); sg[i].y = wave_sum(sg[i].y);
+    if (!grad_only) {
+      sd[i].x = wave_sum(sd[i].x); sd[i].y = wave_sum(sd[i].y);
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      g[((size_t)c * N + s) * 4 + i] = sg[i];
+      if (!grad_only) D[((size_t)c * N + s) * 4 + i] = sd[i];
+    }
   }
 }
 
@@ -195,7 +262,9 @@ k_jtj_expand(const float2* __restrict__ D, const float2* __restrict__ g,
   JtJ[(size_t)c * P * P + ((size_t)8 * s1 + row) * P + 8 * s2 + col] = val;
 }
 
-// Per-chunk weighted model cost: cost[c] += w*|x - J1 C J2^H|^2.
+// Per-row weighted model cost e2[r] = w*|x - J1 C J2^H|^2 (0 for flagged
+// pairs); k_slot_cost and k_chunk_cost sum the rows of each chunk in a
+// fixed order, so the per-chunk cost is reproducible (no float atomics).
 extern "C" __global__ void __launch_bounds__(256)
 k_model_cost(const float2* __restrict__ x, const float2* __restrict__ coh,
              const float2* __restrict__ J,
@@ -203,15 +272,14 @@ k_model_cost(const float2* __restrict__ x, const float2* __restrict__ coh,
              const int* __restrict__ chunk_tab,
              const float* __restrict__ wts,
              int Nbase, int T, int N, int nseg,
-             float* __restrict__ cost) {
+             float* __restrict__ e2) {
   const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t B = (size_t)nseg * T * Nbase;
   float cst = 0.f;
-  int c = 0;
   if (r < B) {
     const int b = (int)(r % Nbase);
     const int st = (int)(r / Nbase);     // seg*T + t
-    c = chunk_tab[st];
+    const int c = chunk_tab[st];
     const int p = pairs[2 * b], q = pairs[2 * b + 1];
     if (p >= 0) {
       cf J1[4], J2[4], C[4], G1[4], V[4];
@@ -230,17 +298,50 @@ k_model_cost(const float2* __restrict__ x, const float2* __restrict__ coh,
         cst += wt * cabs2(d);
       }
     }
+    e2[r] = cst;
   }
-  // block-level reduction per chunk would need sorting; chunk runs are
-  // Nbase-long (>= 190 rows), so lane-0-per-wave atomics after a same-chunk
-  // wave check keep atomic traffic low.
-  const bool uniform = __all(c == __shfl(c, 0, WAVE));
-  if (uniform) {
-    cst = wave_sum(cst);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && cst != 0.f) atomicAdd(&cost[c], cst);
-  } else if (cst != 0.f) {
-    atomicAdd(&cost[c], cst);
+}
+
+// fixed-order sum of one value per thread over a 256-thread block
+__device__ __forceinline__ float block_sum256(float s) {
+  __shared__ float ws[256 / WAVE];
+  const int tid = threadIdx.x;
+  s = wave_sum(s);
+  if ((tid & (WAVE - 1)) == 0) ws[tid / WAVE] = s;
+  __syncthreads();
+  float tot = 0.f;
+#pragma unroll
+  for (int i = 0; i < 256 / WAVE; ++i) tot += ws[i];
+  return tot;
+}
+
+// slot_cost[st] = sum of e2 over the Nbase rows of (seg, t) slot st: one
+// block per slot, threads stride the rows.
+extern "C" __global__ void __launch_bounds__(256)
+k_slot_cost(const float* __restrict__ e2, int Nbase,
+            float* __restrict__ slot_cost) {
+  const int st = blockIdx.x;
+  const float* row = e2 + (size_t)st * Nbase;
+  float s = 0.f;
+  for (int b = threadIdx.x; b < Nbase; b += 256) s += row[b];
+  s = block_sum256(s);
+  if (threadIdx.x == 0) slot_cost[st] = s;
+}
+
+// cost[c] = sum of slot_cost over the slots of chunk c: one block per
+// chunk, threads stride the slot table (independent loads, no serial
+// scan), other chunks' slots contribute 0.
+extern "C" __global__ void __launch_bounds__(256)
+k_chunk_cost(const float* __restrict__ slot_cost,
+             const int* __restrict__ chunk_tab, int nslots,
+             float* __restrict__ cost) {
+  const int c = blockIdx.x;
+  float s = 0.f;
+  for (int st = threadIdx.x; st < nslots; st += 256) {
+    if (chunk_tab[st] == c) s += slot_cost[st];
   }
+  s = block_sum256(s);
+  if (threadIdx.x == 0) cost[c] = s;
 }
 
 // Model application: V[r] (sub=0) or residual x - sum_ci V (sub=1).

@@ -27,12 +27,18 @@ hipError_t launch_predict_coh(
 
 hipError_t launch_jtj_accum(
     const float2* x, const float2* coh, const float2* J, const int* pairs,
-    const int* chunk_tab, const float* wts, int Nbase, int T, int N,
-    int nseg, float2* D, float2* g, float2* Cx, float* cost, int npair,
+    const int* chunk_tab, const int* pidx, const float* wts, int Nbase,
+    int T, int N, int nseg, int Mt, float2* PD, float2* Pg, float* Pc,
+    int* present, float2* D, float2* g, float2* Cx, float* cost, int npair,
     int grad_only, hipStream_t stream) {
+  // store pass (one slot per chunk and pair), then the per-station and
+  // per-chunk sum pass; D, g, cost and present arrive zeroed
   hipLaunchKernelGGL(k_jtj_accum, dim3(Nbase, nseg), dim3(64), 0, stream,
-      x, coh, J, pairs, chunk_tab, wts, Nbase, T, N, D, g, Cx, cost, npair,
-      grad_only);
+      x, coh, J, pairs, chunk_tab, wts, Nbase, T, N, PD, Pg, Cx, Pc, present,
+      npair, grad_only);
+  hipLaunchKernelGGL(k_jtj_reduce, dim3(N + 1, Mt), dim3(64), 0, stream,
+      PD, Pg, Pc, present, pairs, pidx, N, Nbase, npair, grad_only, D, g,
+      cost);
   return hipGetLastError();
 }
 
@@ -47,12 +53,18 @@ hipError_t launch_jtj_expand(
 hipError_t launch_model_cost(
     const float2* x, const float2* coh, const float2* J, const int* pairs,
     const int* chunk_tab, const float* wts, int Nbase, int T, int N,
-    int nseg, float* cost, hipStream_t stream) {
+    int nseg, int Mt, float* e2, float* cost, hipStream_t stream) {
   const long long B = (long long)nseg * T * Nbase;
   const int tb = 256;
   const int nb = (int)((B + tb - 1) / tb);
   hipLaunchKernelGGL(k_model_cost, dim3(nb), dim3(tb), 0, stream,
-      x, coh, J, pairs, chunk_tab, wts, Nbase, T, N, nseg, cost);
+      x, coh, J, pairs, chunk_tab, wts, Nbase, T, N, nseg, e2);
+  // e2 holds B per-row costs followed by nseg*T per-slot sums
+  float* slot_cost = e2 + B;
+  hipLaunchKernelGGL(k_slot_cost, dim3(nseg * T), dim3(tb), 0, stream,
+      e2, Nbase, slot_cost);
+  hipLaunchKernelGGL(k_chunk_cost, dim3(Mt), dim3(tb), 0, stream,
+      slot_cost, chunk_tab, nseg * T, cost);
   return hipGetLastError();
 }
 

@@ -324,7 +324,7 @@ def lbfgs_cost_grad(x, cohs, J_packed, chunk_off, nchunks, bb, T, Nbase,
     for ci in range(M):
         xsub = (rtot + Vs[ci]).contiguous()
         gci, _ = ext.jtr_grad(xsub, cohs4[ci].contiguous(), Jc, lay.pairs,
-                              cts[ci], scale, Nbase, T, N, 1, Mt)
+                              cts[ci], lay.pidx, scale, Nbase, T, N, 1, Mt)
         grad += gci
     g = -2.0 * torch.view_as_real(grad).reshape(-1)
     return cost.to(torch.float32), g

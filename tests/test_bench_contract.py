@@ -47,6 +47,59 @@ def test_bench_default_contract():
     assert d['config']['stations'] == 8
 
 
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes what the last timed step returned as
+    float32/float64 .npy files, identical from run to run (same
+    arguments -> same inputs); --full is accepted and keeps the result
+    line's contract."""
+    import numpy as np
+    small = ['--stations', '8', '--dirs', '2', '--srcs', '2',
+             '--tilesz', '4', '--chan', '2', '--intervals', '2']
+    dumps = []
+    for tag, extra in (('a', []), ('b', ['--full'])):
+        out = tmp_path / tag
+        d = _run_bench(small + ['--dump-outputs', str(out)] + extra)
+        _check(d)
+        assert d['steps'] == 1
+        dumps.append({f: np.load(out / f) for f in sorted(os.listdir(out))})
+    a, b = dumps
+    assert sorted(a) == ['jones.npy', 'res.npy', 'residuals.npy']
+    assert sorted(b) == sorted(a)
+    rows = 8 * 7 // 2 * 4 * 2                 # baselines x slots x intervals
+    assert a['residuals.npy'].shape == (2, rows, 2, 2, 2)   # [F,B,2,2,re/im]
+    assert a['jones.npy'].shape == (2 * 2, 8, 2, 2, 2)      # [Mt,N,2,2,re/im]
+    assert a['res.npy'].shape == (2,) and a['res.npy'][1] < a['res.npy'][0]
+    total = 0
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64), (f, a[f].dtype)
+        assert np.isfinite(a[f]).all(), f
+        assert np.array_equal(a[f], b[f]), f
+        total += a[f].nbytes
+    assert total <= 64 * 2**20
+
+
+def test_bench_dump_outputs_sampling():
+    """An array over its share of the dump budget is cut to a fixed,
+    seeded sample: same entries every time, complex pairs kept whole."""
+    import numpy as np
+    import torch
+    import bench as bench_mod
+    big = torch.arange(3 * 2**21, dtype=torch.float32)
+    big = torch.complex(big, -big).reshape(3, -1)
+    import tempfile
+    with tempfile.TemporaryDirectory() as td:
+        bench_mod.dump_outputs(td, {'big': big, 'one': torch.ones(3)})
+        s1 = np.load(os.path.join(td, 'big.npy'))
+        bench_mod.dump_outputs(td, {'big': big, 'one': torch.ones(3)})
+        s2 = np.load(os.path.join(td, 'big.npy'))
+        one = np.load(os.path.join(td, 'one.npy'))
+    assert s1.dtype == np.float32 and s1.ndim == 2 and s1.shape[1] == 2
+    assert s1.nbytes <= bench_mod.DUMP_BUDGET // 2 < big.numel() * 8
+    assert np.array_equal(s1, s2)
+    assert np.array_equal(s1[:, 0], -s1[:, 1])
+    assert np.array_equal(one, np.ones(3, dtype=np.float32))
+
+
 def test_bench_rtr_contract():
     d = _run_bench(['--stations', '48', '--dirs', '2', '--srcs', '2',
                     '--tilesz', '2', '--chan', '2', '--solver', 'rtr',

@@ -116,6 +116,102 @@ def test_jtj_jtr_chunked(problem):
     assert float(errg) < 2e-5
 
 
+def test_jtj_cost_segments_reproducible():
+    """Store-and-sum accumulation at a shape the small fixture does not
+    reach: N=70 (> one 64-lane pass over partner stations, not a multiple),
+    two segments with two uneven time chunks each, weights, and two
+    flagged baselines whose slots are never written (the scratch is
+    poisoned with NaN first, and the cached pair-index table still lists
+    them, so both skip paths run). JtJ, Jtr and the PER-CHUNK costs of
+    both kernels match the fp64 reference, and a second call returns
+    bitwise the same (no arrival-order sums). A gradient-only launch over
+    segment 0 alone must fill chunks 0-1 and leave chunks 2-3 zero."""
+    from sagecal_amd.ops import reference as R
+    from sagecal_amd.ops.hip_host import (BaselineLayout, jtj_jtr,
+                                          model_cost_per_chunk, _ext, _c64)
+    dev = 'cuda:0'
+    rng = np.random.default_rng(12)
+    N, T, nseg, nchunk = 70, 5, 2, 4
+    pairs = np.array([(p, q) for p in range(N) for q in range(p + 1, N)])
+    Nbase = len(pairs)
+    B = nseg * T * Nbase
+    bb = torch.tensor(np.tile(pairs, (nseg * T, 1)))
+    slot = np.arange(nseg * T)
+    rows = torch.tensor(np.repeat(2 * (slot // T) + (slot % T >= 3), Nbase))
+
+    def cplx(*shape):
+        return torch.tensor(rng.standard_normal(shape)
+                            + 1j * rng.standard_normal(shape))
+    x, coh = cplx(B, 2, 2), cplx(B, 2, 2)
+    J = torch.tensor(np.eye(2)[None, None]) + 0.2 * cplx(nchunk, N, 2, 2)
+    w = torch.tensor(rng.uniform(0.5, 2.0, B))
+    flagged = (7, 2000)                  # pair indices; reference: weight 0
+    bbf = bb.clone()
+    for k in flagged:
+        w[k::Nbase] = 0.0
+        bbf[k::Nbase] = -1
+    JtJ_r, Jtr_r, _ = R.jtj_jtr(x, coh, J, bb, N, w, rows, nchunk)
+    r = x - R.apply_jones(coh, J, bb, rows)
+    e2 = w * (r.abs() ** 2).sum(dim=(-1, -2))
+    cost_r = torch.zeros(nchunk, dtype=torch.float64).index_add_(0, rows, e2)
+
+    BaselineLayout(bb.to(dev), Nbase, T, nseg, N, dev)   # caches full pidx
+    lay = BaselineLayout(bbf.to(dev), Nbase, T, nseg, N, dev)
+    assert int(lay.pidx[0, 8]) == 7 and int(lay.pairs[7, 0]) == -1
+    xg = x.to(device=dev, dtype=torch.complex64)
+    cg = coh.to(device=dev, dtype=torch.complex64)
+    Jg = J.to(device=dev, dtype=torch.complex64)
+    wg = torch.tensor(rng.uniform(0.5, 2.0, B)).to(
+        device=dev, dtype=torch.float32)     # nonzero on flagged rows too
+    keep = torch.ones(B, dtype=torch.bool)
+    for k in flagged:
+        keep[k::Nbase] = False
+    wg[keep.to(dev)] = w[keep].to(device=dev, dtype=torch.float32)
+    rg = rows.to(dev)
+
+    def poison():
+        # freed NaN blocks of the scratch sizes: the caching allocator
+        # hands them to the next torch::empty of that size
+        for shape, dt in (((nchunk * Nbase, 8), torch.complex64),
+                          ((nchunk * Nbase, 8), torch.complex64),
+                          ((nchunk * Nbase,), torch.float32)):
+            torch.full(shape, float('nan'), dtype=dt, device=dev)
+    outs = []
+    for _ in range(2):
+        poison()
+        JtJ_g, Jtr_g, cost_g = _ext().jtj_jtr(
+            _c64(xg), _c64(cg), Jg.reshape(-1, 4).contiguous(), lay.pairs,
+            lay.chunk_tab(rg), lay.pidx, wg, Nbase, T, N, nseg, nchunk)
+        mc_g = model_cost_per_chunk(xg, cg, Jg, bb.to(dev), N, wg, rg,
+                                    nchunk, lay)
+        outs.append((JtJ_g, Jtr_g, cost_g, mc_g))
+    for a, b2 in zip(*outs):
+        assert torch.equal(a, b2)
+    JtJ_g, Jtr_g, cost_g, mc_g = outs[0]
+    # fp32 sums of up to 3*2415 O(10) terms against fp64: ~1e-6 relative
+    err = (JtJ_g.cpu().double() - JtJ_r).abs().max() / JtJ_r.abs().max()
+    assert float(err) < 2e-5, float(err)
+    errg = (Jtr_g.cpu().double() - Jtr_r).abs().max() / Jtr_r.abs().max()
+    assert float(errg) < 2e-5, float(errg)
+    assert torch.allclose(cost_g.cpu().double(), cost_r, rtol=1e-5)
+    assert torch.allclose(mc_g.cpu().double(), cost_r, rtol=1e-5)
+
+    # gradient-only launch that covers a subset of the chunks: segment 0
+    # (chunks 0, 1) of Mt=4
+    B0 = T * Nbase
+    lay0 = BaselineLayout(bbf[:B0].to(dev), Nbase, T, 1, N, dev)
+    poison()
+    g, _ = _ext().jtr_grad(
+        _c64(xg[:B0]), _c64(cg[:B0]), Jg.reshape(-1, 4).contiguous(),
+        lay0.pairs, lay0.chunk_tab(rg[:B0]), lay0.pidx, wg[:B0].contiguous(),
+        Nbase, T, N, 1, nchunk)
+    gv = torch.view_as_real(g).reshape(nchunk, 8 * N).cpu().double()
+    assert torch.isfinite(gv).all()
+    assert float(gv[2:].abs().max()) == 0.0
+    errs = (gv[:2] - Jtr_r[:2]).abs().max() / Jtr_r[:2].abs().max()
+    assert float(errs) < 2e-5, float(errs)
+
+
 def test_apply_jones_and_cost(problem):
     from sagecal_amd.ops import reference as R
     from sagecal_amd.ops.hip_host import (BaselineLayout, apply_jones,
@@ -370,9 +466,17 @@ def test_chol_mw_large_n4096():
     A = G @ G.transpose(-1, -2) + 0.5 * torch.eye(n, device=dev)
     b = torch.randn(batch, n, device=dev)
     mu = torch.full((batch,), 0.1, device=dev)
-    dp = chol_solve_damped(A, b, mu)
-    Ad = (A + mu[:, None, None] * torch.eye(n, device=dev)).double()
+    # the copy to the host synchronises: a fault in the kernel sequence
+    # is reported on this line
+    dp = chol_solve_damped(A, b, mu).double().cpu()
+    # fp64 reference on the host: with the reference on the device this
+    # test died with a launch failure reported at torch's batched fp64
+    # cholesky_solve, after torch.linalg.cholesky had synchronised. The
+    # cause of that failure is not established; the host reference only
+    # keeps torch's device solve out of the test
+    Ad = A.double().cpu() + mu.double().cpu()[:, None, None] * torch.eye(
+        n, dtype=torch.float64)
     L = torch.linalg.cholesky(Ad)
-    ref = torch.cholesky_solve(b.double().unsqueeze(-1), L).squeeze(-1)
-    err = (dp.double() - ref).abs().max() / ref.abs().max()
+    ref = torch.cholesky_solve(b.double().cpu().unsqueeze(-1), L).squeeze(-1)
+    err = (dp - ref).abs().max() / ref.abs().max()
     assert float(err) < 5e-2, float(err)   # fp32 kernel vs fp64 at n=4096
