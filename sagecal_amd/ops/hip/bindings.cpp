@@ -25,9 +25,9 @@ hipError_t launch_apply_jones(const float2*, const float2*, const float2*,
     const int*, const int*, int, int, int, int, int, int, float2*,
     hipStream_t);
 hipError_t launch_chol_mw(const float*, const float*, const float*, int,
-                          int, float*, float*, int*, int, hipStream_t);
+                          int, float*, float*, int*, hipStream_t);
 hipError_t launch_chol_solve(const float*, const float*, const float*, int,
-    int, float*, float*, int*, int, hipStream_t);
+    int, float*, float*, int*, hipStream_t);
 }
 
 #define CHECK_HIP(x) do { hipError_t e = (x); TORCH_CHECK(e == hipSuccess, \
@@ -148,37 +148,46 @@ torch::Tensor apply_jones(
   return out;
 }
 
-std::vector<torch::Tensor> chol_solve(
-    torch::Tensor JtJ, torch::Tensor Jtr, torch::Tensor mu,
-    torch::Tensor scratch, int64_t stages) {
+using chol_launcher_t = hipError_t (*)(const float*, const float*,
+    const float*, int, int, float*, float*, int*, hipStream_t);
+
+// dp = (JtJ + mu I)^-1 Jtr through either Cholesky launcher (same
+// contract); scratch holds 2*n*n floats per problem
+static std::vector<torch::Tensor> chol_solve_with(
+    chol_launcher_t launch, torch::Tensor JtJ, torch::Tensor Jtr,
+    torch::Tensor mu, torch::Tensor scratch) {
+  TORCH_CHECK(JtJ.dim() == 3 && JtJ.size(1) == JtJ.size(2),
+              "JtJ must be [batch, n, n]");
   const int64_t batch = JtJ.size(0);
   const int64_t n = JtJ.size(1);
+  TORCH_CHECK(Jtr.dim() == 2 && Jtr.size(0) == batch && Jtr.size(1) == n,
+              "Jtr must be [batch, n]");
+  TORCH_CHECK(mu.dim() == 1 && mu.size(0) == batch, "mu must be [batch]");
+  TORCH_CHECK(JtJ.is_contiguous() && Jtr.is_contiguous() &&
+              mu.is_contiguous() && scratch.is_contiguous(),
+              "JtJ, Jtr, mu and scratch must be contiguous");
+  TORCH_CHECK(scratch.numel() >= batch * 2 * n * n,
+              "scratch must hold batch * 2 * n * n floats");
   auto dp = torch::empty({batch, n},
       torch::dtype(torch::kFloat).device(JtJ.device()));
   auto info = torch::zeros({batch},
       torch::dtype(torch::kInt).device(JtJ.device()));
-  CHECK_HIP(launch_chol_solve(JtJ.data_ptr<float>(), Jtr.data_ptr<float>(),
+  CHECK_HIP(launch(JtJ.data_ptr<float>(), Jtr.data_ptr<float>(),
       mu.data_ptr<float>(), (int)n, (int)batch, scratch.data_ptr<float>(),
-      dp.data_ptr<float>(), info.data_ptr<int>(), (int)stages,
-      cur_stream()));
+      dp.data_ptr<float>(), info.data_ptr<int>(), cur_stream()));
   return {dp, info};
+}
+
+std::vector<torch::Tensor> chol_solve(
+    torch::Tensor JtJ, torch::Tensor Jtr, torch::Tensor mu,
+    torch::Tensor scratch) {
+  return chol_solve_with(launch_chol_solve, JtJ, Jtr, mu, scratch);
 }
 
 std::vector<torch::Tensor> chol_solve_mw(
     torch::Tensor JtJ, torch::Tensor Jtr, torch::Tensor mu,
-    torch::Tensor scratch, int64_t stages) {
-  // multi-workgroup right-looking path: same contract as chol_solve
-  const int64_t batch = JtJ.size(0);
-  const int64_t n = JtJ.size(1);
-  auto dp = torch::empty({batch, n},
-      torch::dtype(torch::kFloat).device(JtJ.device()));
-  auto info = torch::zeros({batch},
-      torch::dtype(torch::kInt).device(JtJ.device()));
-  CHECK_HIP(launch_chol_mw(JtJ.data_ptr<float>(), Jtr.data_ptr<float>(),
-      mu.data_ptr<float>(), (int)n, (int)batch, scratch.data_ptr<float>(),
-      dp.data_ptr<float>(), info.data_ptr<int>(), (int)stages,
-      cur_stream()));
-  return {dp, info};
+    torch::Tensor scratch) {
+  return chol_solve_with(launch_chol_mw, JtJ, Jtr, mu, scratch);
 }
 
 std::vector<torch::Tensor> jtr_grad(

@@ -80,12 +80,19 @@ hipError_t launch_apply_jones(
   return hipGetLastError();
 }
 
+// shape contract shared by both Cholesky launchers (see cholesky.hip):
+// violated, the kernels would run float4 traffic out of bounds or ask for
+// more LDS than a CU has
+static bool chol_shape_ok(int n, int batch, int maxn) {
+  return n > 0 && n % NB == 0 && n <= maxn && batch > 0;
+}
+
 hipError_t launch_chol_solve(
     const float* JtJ, const float* Jtr, const float* mu, int n, int batch,
-    float* Lbuf, float* dp, int* info, int stages, hipStream_t stream) {
-  const size_t shmem = (size_t)(n + 40) * PST * sizeof(float);
-  hipLaunchKernelGGL(k_chol_solve, dim3(batch), dim3(512), shmem, stream,
-      JtJ, Jtr, mu, n, Lbuf, dp, info, stages);
+    float* Lbuf, float* dp, int* info, hipStream_t stream) {
+  if (!chol_shape_ok(n, batch, MAXN_CHOL)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_chol_solve, dim3(batch), dim3(NTH),
+      chol_solve_lds_bytes(n), stream, JtJ, Jtr, mu, n, Lbuf, dp, info);
   return hipGetLastError();
 }
 
@@ -93,31 +100,29 @@ hipError_t launch_chol_solve(
 // (graph-capturable). See cholesky.hip for the rationale.
 hipError_t launch_chol_mw(
     const float* JtJ, const float* Jtr, const float* mu, int n, int batch,
-    float* Lbuf, float* dp, int* info, int stages, hipStream_t stream) {
-  hipLaunchKernelGGL(k_cholmw_init, dim3(batch, INIT_SLICES), dim3(512), 0,
+    float* Lbuf, float* dp, int* info, hipStream_t stream) {
+  if (!chol_shape_ok(n, batch, MAXN_CHOL_MW)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cholmw_init, dim3(batch, INIT_SLICES), dim3(NTH), 0,
       stream, JtJ, Jtr, mu, n, Lbuf, dp);
-  if (stages < 2) return hipGetLastError();
-  // n <= PANEL_CAP: the hardware-validated single-pass panel kernel;
-  // larger n: the chunked-panel variant (row passes through LDS)
-  const int cap = n < PANEL_CAP ? n : PANEL_CAP;
-  const size_t shmem = (size_t)(cap + 8) * PST * sizeof(float);
+  // n <= PANEL_CAP: the single-pass panel kernel; larger n: the
+  // chunked-panel variant (row passes through LDS)
+  const size_t shmem = cholmw_panel_lds_bytes(n);
   for (int k = 0; k < n; k += NB) {
     if (n <= PANEL_CAP) {
-      hipLaunchKernelGGL(k_cholmw_panel, dim3(batch), dim3(512), shmem,
+      hipLaunchKernelGGL(k_cholmw_panel, dim3(batch), dim3(NTH), shmem,
           stream, n, k, Lbuf, dp, info);
     } else {
-      hipLaunchKernelGGL(k_cholmw_panel_big, dim3(batch), dim3(512),
+      hipLaunchKernelGGL(k_cholmw_panel_big, dim3(batch), dim3(NTH),
           shmem, stream, n, k, Lbuf, dp, info);
     }
     const int tcnt = (n - k - NB) / NB;
     const int ntiles = tcnt * (tcnt + 1) / 2;
-    if (ntiles > 0 && stages >= 3) {
+    if (ntiles > 0) {
       hipLaunchKernelGGL(k_cholmw_syrk, dim3(batch * ntiles), dim3(64), 0,
           stream, n, k, ntiles, Lbuf);
     }
   }
-  if (stages < 4) return hipGetLastError();
-  hipLaunchKernelGGL(k_cholmw_subst, dim3(batch), dim3(512), 0, stream,
+  hipLaunchKernelGGL(k_cholmw_subst, dim3(batch), dim3(NTH), 0, stream,
       n, Lbuf, dp, info);
   return hipGetLastError();
 }

@@ -357,7 +357,7 @@ def chol_solve_damped(JtJ, Jtr, mu):
             _chol_scratch.pop(next(iter(_chol_scratch)))
         sc = torch.empty(want, dtype=JtJ.dtype, device=JtJ.device)
         _chol_scratch[key] = sc
-    # n >= 256: multi-workgroup right-looking path — the trailing-update
+    # n >= 384: multi-workgroup right-looking path — the trailing-update
     # SYRK tiles spread over the whole chip instead of 1 WG/problem
     # (65% of step time at [5,512,512]; see profiles/). Small n stays on
     # the single fused kernel (lower launch count wins).
@@ -368,10 +368,10 @@ def chol_solve_damped(JtJ, Jtr, mu):
         assert JtJ.shape[1] <= 4096, "mw Cholesky supports n <= 4096"
         dp, info = _ext().chol_solve_mw(JtJ.contiguous(), Jtr.contiguous(),
                                         mu.to(torch.float32).contiguous(),
-                                        sc, 4)
+                                        sc)
     else:
         dp, info = _ext().chol_solve(JtJ.contiguous(), Jtr.contiguous(),
                                      mu.to(torch.float32).contiguous(),
-                                     sc, 3)
+                                     sc)
     # failed factorizations already return NaN rows (kernel poisons dp)
     return dp[:, :n]

@@ -358,7 +358,7 @@ def test_lbfgs_cost_grad_gpu():
 
 def test_chol_mw_matches_single_kernel():
     """Multi-workgroup right-looking path vs the fused single-WG kernel
-    (same scratch contract; dispatch picks mw for 384<=n<=576)."""
+    (same scratch contract; dispatch picks mw for n >= 384)."""
     import sagecal_amd.ops.hip.dirac_hip as ext
     dev = 'cuda:0'
     rng = np.random.default_rng(5)
@@ -371,11 +371,81 @@ def test_chol_mw_matches_single_kernel():
                      device=dev).contiguous()
     mu = torch.full((batch,), 0.1, device=dev)
     sc = torch.empty(batch, 2 * n * n, dtype=torch.float32, device=dev)
-    x1, i1 = ext.chol_solve(A, b, mu, sc, 3)
-    x2, i2 = ext.chol_solve_mw(A, b, mu, sc, 4)
+    x1, i1 = ext.chol_solve(A, b, mu, sc)
+    x2, i2 = ext.chol_solve_mw(A, b, mu, sc)
     assert int(i1.sum()) == 0 and int(i2.sum()) == 0
     err = (x1 - x2).abs().max() / x1.abs().max()
     assert float(err) < 1e-4, f"mw vs single rel err {float(err)}"
+
+
+def _chol_problem(rng, n, batch):
+    """fp32 (A, b, mu) with A = G G^T / n + 0.5 I, and the fp64 host
+    solution of (A + mu I) x = b for those fp32 inputs."""
+    G = rng.standard_normal((batch, n, n))
+    A = torch.tensor(G @ G.transpose(0, 2, 1) / n + 0.5 * np.eye(n),
+                     dtype=torch.float32)
+    b = torch.tensor(rng.standard_normal((batch, n)), dtype=torch.float32)
+    mu = torch.tensor(rng.uniform(0.01, 1.0, batch), dtype=torch.float32)
+    ref = torch.linalg.solve(
+        A.double() + mu.double()[:, None, None] * torch.eye(n).double(),
+        b.double().unsqueeze(-1)).squeeze(-1)
+    return A, b, mu, ref
+
+
+def _chol_direct(entry, A, b, mu, dev='cuda:0'):
+    batch, n = b.shape
+    sc = torch.empty(batch, 2 * n * n, dtype=torch.float32, device=dev)
+    dp, info = entry(A.to(dev), b.to(dev), mu.to(dev), sc)
+    return dp.cpu().double(), info.cpu()
+
+
+def test_chol_small_and_chunked_shapes():
+    """Both Cholesky entry points, called directly, vs an fp64 host solve:
+    n=32 is a single panel (the left-looking update never runs), n=64 has
+    one update and one SYRK tile, n=96 three SYRK tiles (one off-diagonal:
+    the tile-index decode), and n=1088 takes the chunked panel kernel with
+    two panels of 1024+64 and 1024+32 rows before the single-pass ones.
+    Shapes outside the kernels' contract are refused before any launch."""
+    import sagecal_amd.ops.hip.dirac_hip as ext
+    rng = np.random.default_rng(31)
+    fused, mw = ext.chol_solve, ext.chol_solve_mw
+    for n, batch, entries in ((32, 3, (fused,)), (64, 3, (fused, mw)),
+                              (96, 3, (fused, mw)), (1088, 2, (mw,))):
+        A, b, mu, ref = _chol_problem(rng, n, batch)
+        for entry in entries:
+            dp, info = _chol_direct(entry, A, b, mu)
+            err = float((dp - ref).abs().max() / ref.abs().max())
+            name = 'mw' if entry is mw else 'fused'
+            print(f"{name} n={n} batch={batch}: rel err {err:.3e}")
+            assert info.tolist() == [0] * batch, (name, n, info.tolist())
+            assert err < 1e-3, f"{name} n={n} batch={batch}: rel err {err}"
+    # n not a multiple of 32, and n above the fused kernel's 1024
+    for n in (48, 1056):
+        A = torch.eye(n).unsqueeze(0)
+        with pytest.raises(RuntimeError):
+            _chol_direct(fused, A, torch.ones(1, n), torch.full((1,), 0.1))
+
+
+def test_chol_failed_factorization_is_contained():
+    """A problem whose first pivot is negative (-I with mu = 0.1) comes
+    back as a NaN row with info = 1; its neighbours in the batch are
+    solved as usual."""
+    import sagecal_amd.ops.hip.dirac_hip as ext
+    n, batch = 64, 3
+    A, b, _, _ = _chol_problem(np.random.default_rng(32), n, batch)
+    A[1] = -torch.eye(n)
+    mu = torch.full((batch,), 0.1)
+    good = [0, 2]
+    ref = torch.linalg.solve(
+        A[good].double() + float(mu[0]) * torch.eye(n).double(),
+        b[good].double().unsqueeze(-1)).squeeze(-1)
+    for entry in (ext.chol_solve, ext.chol_solve_mw):
+        dp, info = _chol_direct(entry, A, b, mu)
+        assert info.tolist() == [0, 1, 0]
+        assert torch.isnan(dp[1]).all()
+        err = (dp[good] - ref).abs().max(dim=1).values / \
+            ref.abs().max(dim=1).values
+        assert float(err.max()) < 1e-3, err.tolist()
 
 
 @pytest.mark.skipif(os.environ.get('SAGECAL_RTR_GRAPH', '1') == '0',

@@ -55,7 +55,7 @@ static int test_chol(int n) {
   CHK(hipMemcpy(db, b.data(), sizeof(float) * n, hipMemcpyHostToDevice));
   CHK(hipMemcpy(dmu, &mu_h, sizeof(float), hipMemcpyHostToDevice));
   CHK(hipMemset(dinfo, 0, sizeof(int)));
-  CHK(launch_chol_mw(dA, db, dmu, n, batch, dL, dx, dinfo, 4, 0));
+  CHK(launch_chol_mw(dA, db, dmu, n, batch, dL, dx, dinfo, 0));
   CHK(hipDeviceSynchronize());
   std::vector<float> x(n);
   int info_h = 0;
@@ -205,7 +205,7 @@ static int test_chol_graph(int n) {
   hipGraph_t graph;
   hipGraphExec_t gexec;
   CHK(hipStreamBeginCapture(st, hipStreamCaptureModeGlobal));
-  CHK(launch_chol_mw(dA, db, dmu, n, batch, dL, dx, dinfo, 4, st));
+  CHK(launch_chol_mw(dA, db, dmu, n, batch, dL, dx, dinfo, st));
   CHK(hipStreamEndCapture(st, &graph));
   CHK(hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
   CHK(hipGraphLaunch(gexec, st));
