@@ -12,6 +12,13 @@ hipError_t launch_predict_coh(const double*, const double*, const double*,
     const float*, const int*, const int*, int, int, double, double,
     double, const float*, const int*, int, int, int, float2*,
     hipStream_t);
+hipError_t launch_shapelet_coh(const double*, const double*, const double*,
+    int, int, const int*, const int*, const int*, const float*, const int*,
+    const float*, const float*, const float*, const float*, const float*,
+    const float*, const float*, const float*, const float*, const float*,
+    const double*, const double*, const double*, const float*, int,
+    const float*, const float*, double, double, double, const float*,
+    const int*, int, int, int, float2*, hipStream_t);
 hipError_t launch_jtj_accum(const float2*, const float2*, const float2*,
     const int*, const int*, const int*, const float*, int, int, int, int,
     int, float2*, float2*, float*, int*, float2*, float2*, float2*, float*,
@@ -81,6 +88,89 @@ torch::Tensor predict_coh(
       fdelta2, tdelta, beam_p, pairs_p, (int)Nbase, Ktot, Nsta,
       cptr(out), cur_stream()));
   return out;
+}
+
+// Adds the shapelet sources of a ShapeletTable (hip_host.py) into `out`
+// [M, R, 4] complex64, in place, on the current stream.
+void shapelet_coh_add(
+    torch::Tensor out, torch::Tensor u, torch::Tensor v, torch::Tensor w,
+    torch::Tensor src, torch::Tensor cluster, torch::Tensor n0,
+    torch::Tensor beta, torch::Tensor off, torch::Tensor coef,
+    torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
+    torch::Tensor sphi, torch::Tensor psign, torch::Tensor a,
+    torch::Tensor b, torch::Tensor ceP, torch::Tensor seP,
+    torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
+    torch::Tensor rec, torch::Tensor flux, torch::Tensor r1,
+    double freq, double fdelta2, double tdelta,
+    c10::optional<torch::Tensor> beam, c10::optional<torch::Tensor> pairs,
+    int64_t Nbase) {
+  const int64_t R = u.size(0);
+  const int64_t S = src.size(0);
+  auto chk = [&](const torch::Tensor& t, torch::ScalarType ty, int64_t n,
+                 const char* name) {
+    TORCH_CHECK(t.device() == out.device(), name, " is on another device");
+    TORCH_CHECK(t.scalar_type() == ty, name, " has the wrong dtype");
+    TORCH_CHECK(t.is_contiguous() && t.numel() == n, name,
+                " must be contiguous with ", n, " elements");
+  };
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kComplexFloat &&
+              out.is_contiguous() && out.dim() == 3 && out.size(1) == R &&
+              out.size(2) == 4, "out must be contiguous [M, R, 4] complex64");
+  chk(u, torch::kDouble, R, "u");
+  chk(v, torch::kDouble, R, "v");
+  chk(w, torch::kDouble, R, "w");
+  chk(src, torch::kInt, S, "src");
+  chk(cluster, torch::kInt, S, "cluster");
+  chk(n0, torch::kInt, S, "n0");
+  chk(beta, torch::kFloat, S, "beta");
+  chk(off, torch::kInt, S + 1, "off");
+  TORCH_CHECK(coef.scalar_type() == torch::kFloat && coef.is_contiguous() &&
+              coef.device() == out.device(), "coef must be contiguous float32");
+  chk(cxi, torch::kFloat, S, "cxi");
+  chk(sxi, torch::kFloat, S, "sxi");
+  chk(cphi, torch::kFloat, S, "cphi");
+  chk(sphi, torch::kFloat, S, "sphi");
+  chk(psign, torch::kFloat, S, "psign");
+  chk(a, torch::kFloat, S, "a");
+  chk(b, torch::kFloat, S, "b");
+  chk(ceP, torch::kFloat, S, "ceP");
+  chk(seP, torch::kFloat, S, "seP");
+  chk(ll, torch::kDouble, S, "ll");
+  chk(mm, torch::kDouble, S, "mm");
+  chk(nn1, torch::kDouble, S, "nn1");
+  TORCH_CHECK(rec.dim() == 2 && rec.size(0) == 2, "rec must be [2, max n0]");
+  chk(rec, torch::kFloat, rec.numel(), "rec");
+  chk(flux, torch::kFloat, 4 * S, "flux");
+  chk(r1, torch::kFloat, S, "r1");
+  const float* beam_p = nullptr;
+  const int* pairs_p = nullptr;
+  int Ktot = 0, Nsta = 0;
+  if (beam.has_value()) {
+    TORCH_CHECK(pairs.has_value(), "beam needs the station-pair table");
+    TORCH_CHECK(beam->is_contiguous() && beam->dim() == 3 &&
+                beam->scalar_type() == torch::kFloat &&
+                beam->device() == out.device(),
+                "beam must be contiguous [T, K, N] float32");
+    TORCH_CHECK(Nbase > 0 && R <= beam->size(0) * Nbase,
+                "beam has too few timeslots for the rows");
+    chk(*pairs, torch::kInt, 2 * Nbase, "pairs");
+    beam_p = beam->data_ptr<float>();
+    pairs_p = pairs->data_ptr<int>();
+    Ktot = beam->size(1);
+    Nsta = beam->size(2);
+  }
+  CHECK_HIP(launch_shapelet_coh(
+      u.data_ptr<double>(), v.data_ptr<double>(), w.data_ptr<double>(),
+      (int)R, (int)S, src.data_ptr<int>(), cluster.data_ptr<int>(),
+      n0.data_ptr<int>(), beta.data_ptr<float>(), off.data_ptr<int>(),
+      coef.data_ptr<float>(), cxi.data_ptr<float>(), sxi.data_ptr<float>(),
+      cphi.data_ptr<float>(), sphi.data_ptr<float>(),
+      psign.data_ptr<float>(), a.data_ptr<float>(), b.data_ptr<float>(),
+      ceP.data_ptr<float>(), seP.data_ptr<float>(), ll.data_ptr<double>(),
+      mm.data_ptr<double>(), nn1.data_ptr<double>(), rec.data_ptr<float>(),
+      (int)rec.size(1), flux.data_ptr<float>(), r1.data_ptr<float>(), freq,
+      fdelta2, tdelta, beam_p, pairs_p, (int)Nbase, Ktot, Nsta, cptr(out),
+      cur_stream()));
 }
 
 std::vector<torch::Tensor> jtj_jtr(
@@ -227,6 +317,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eP"), py::arg("cxi"), py::arg("sxi"), py::arg("cphi"),
         py::arg("sphi"), py::arg("r1"), py::arg("stype"),
         py::arg("cluster_off"), py::arg("freq"), py::arg("fdelta2"),
+        py::arg("tdelta"), py::arg("beam") = py::none(),
+        py::arg("pairs") = py::none(), py::arg("Nbase") = 0);
+  m.def("shapelet_coh_add", &shapelet_coh_add,
+        "add shapelet-source coherencies into out (gfx950)",
+        py::arg("out"), py::arg("u"), py::arg("v"), py::arg("w"),
+        py::arg("src"), py::arg("cluster"), py::arg("n0"), py::arg("beta"),
+        py::arg("off"), py::arg("coef"), py::arg("cxi"), py::arg("sxi"),
+        py::arg("cphi"), py::arg("sphi"), py::arg("psign"), py::arg("a"),
+        py::arg("b"), py::arg("ceP"), py::arg("seP"), py::arg("ll"),
+        py::arg("mm"), py::arg("nn1"), py::arg("rec"), py::arg("flux"),
+        py::arg("r1"), py::arg("freq"), py::arg("fdelta2"),
         py::arg("tdelta"), py::arg("beam") = py::none(),
         py::arg("pairs") = py::none(), py::arg("Nbase") = 0);
   m.def("jtj_jtr", &jtj_jtr, "fused JtJ/Jtr assembly (gfx950)");

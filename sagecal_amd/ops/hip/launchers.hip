@@ -25,6 +25,27 @@ hipError_t launch_predict_coh(
   return hipGetLastError();
 }
 
+hipError_t launch_shapelet_coh(
+    const double* u, const double* v, const double* w, int R, int S,
+    const int* src, const int* cluster, const int* n0, const float* beta,
+    const int* off, const float* coef, const float* cxi, const float* sxi,
+    const float* cphi, const float* sphi, const float* psign,
+    const float* a, const float* b, const float* ceP, const float* seP,
+    const double* ll, const double* mm, const double* nn1,
+    const float* rec, int nmax, const float* flux, const float* r1,
+    double freq, double fdelta2, double tdelta, const float* beam,
+    const int* pairs, int Nbase, int Ktot, int Nsta, float2* out,
+    hipStream_t stream) {
+  if (S <= 0 || R <= 0) return hipSuccess;
+  const int tb = 128;
+  const int nb = (R + tb - 1) / tb;
+  hipLaunchKernelGGL(k_shapelet_coh, dim3(nb), dim3(tb), 0, stream,
+      u, v, w, R, S, src, cluster, n0, beta, off, coef, cxi, sxi, cphi,
+      sphi, psign, a, b, ceP, seP, ll, mm, nn1, rec, nmax, flux, r1,
+      freq, fdelta2, tdelta, beam, pairs, Nbase, Ktot, Nsta, out);
+  return hipGetLastError();
+}
+
 hipError_t launch_jtj_accum(
     const float2* x, const float2* coh, const float2* J, const int* pairs,
     const int* chunk_tab, const int* pidx, const float* wts, int Nbase,

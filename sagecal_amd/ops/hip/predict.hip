@@ -5,7 +5,9 @@
 // through LDS in tiles, fp64 phase arithmetic with double-precision arg
 // reduction followed by fast float sincos. Per-channel fluxes are
 // precomputed on the host (torch), so the kernel carries no spectral-index
-// math; shapelet envelopes are folded in by the host path (shapelet.py).
+// math. Shapelet sources have their fluxes zeroed for k_predict_coh and
+// are added by k_shapelet_coh (below), launched after it on the same
+// stream from a device-resident mode table (hip_host.ShapeletTable).
 //
 // Layout: rows r = t*Nbase + b (time-major); output coh [M, R, 4] complex64.
 //
@@ -27,6 +29,30 @@ struct SrcTile {
   float r1[SRC_TILE];  // time-smear source-distance term (precomputed host)
   int   stype[SRC_TILE];
 };
+
+// Smeared phase term of one source at one row, shared by k_predict_coh and
+// k_shapelet_coh: exp(i*phase) * freq smearing * time smearing.
+__device__ __forceinline__ cf phase_smear(double ur, double vr, double wr,
+                                          double l, double m, double n1,
+                                          double freq, double fdelta2,
+                                          float tsm_c, float r1) {
+  // fp64 phase term G = 2*pi*(u l + v m + w (n-1)) (seconds * none)
+  const double G = 6.283185307179586476925286766559 *
+      (ur * l + vr * m + wr * n1);
+  // phase at this channel, arg-reduced in fp64 then fast float sincos
+  const double ph = fma(G, freq, 0.0);
+  const float phr = (float)fmod(ph, 6.283185307179586476925286766559);
+  float sp, cp;
+  __sincosf(phr, &sp, &cp);
+  // freq smearing |sinc(G*fdelta/2)| (predict.c:178-189)
+  float sm = 1.0f;
+  const float smf = (float)(G * fdelta2);
+  if (fabsf(smf) > 1e-9f) sm = fabsf(__sinf(smf) / smf);
+  // time smearing (predict.c:94-107); r1 precomputed per source
+  const float prod = tsm_c * r1;
+  if (prod > 1e-9f) sm *= 1.0645f * erff(0.8326f * prod) / prod;
+  return {cp * sm, sp * sm};
+}
 
 extern "C" __global__ void __launch_bounds__(128)
 k_predict_coh(const double* __restrict__ u, const double* __restrict__ v,
@@ -89,22 +115,8 @@ k_predict_coh(const double* __restrict__ u, const double* __restrict__ v,
       __syncthreads();
       if (!live) continue;
       for (int k = 0; k < nt; ++k) {
-        // fp64 phase term G = 2*pi*(u l + v m + w (n-1)) (seconds * none)
-        const double G = 6.283185307179586476925286766559 *
-            (ur * tile.ll[k] + vr * tile.mm[k] + wr * tile.nn1[k]);
-        // phase at this channel, arg-reduced in fp64 then fast float sincos
-        const double ph = fma(G, freq, 0.0);
-        const float phr = (float)fmod(ph, 6.283185307179586476925286766559);
-        float sp, cp;
-        __sincosf(phr, &sp, &cp);
-        // freq smearing |sinc(G*fdelta/2)| (predict.c:178-189)
-        float sm = 1.0f;
-        const float smf = (float)(G * fdelta2);
-        if (fabsf(smf) > 1e-9f) sm = fabsf(__sinf(smf) / smf);
-        // time smearing (predict.c:94-107); r1 precomputed per source
-        const float prod = tsm_c * tile.r1[k];
-        if (prod > 1e-9f) sm *= 1.0645f * erff(0.8326f * prod) / prod;
-        cf phc = {cp * sm, sp * sm};
+        cf phc = phase_smear(ur, vr, wr, tile.ll[k], tile.mm[k], tile.nn1[k],
+                             freq, fdelta2, tsm_c, tile.r1[k]);
         // extended-source envelope at wavelength-scaled uvw
         const int st = tile.stype[k];
         if (st != 0) {
@@ -130,7 +142,7 @@ k_predict_coh(const double* __restrict__ u, const double* __restrict__ v,
                             6.2831853071795865f;
             phc = cscale(phc, j0f(b));
           }
-          // st==4 (shapelet): envelope folded in on the host path
+          // st==4 (shapelet): fluxes are zero here, k_shapelet_coh adds them
         }
         if (beam != nullptr) {
           const float* bg = beam +
@@ -153,4 +165,130 @@ k_predict_coh(const double* __restrict__ u, const double* __restrict__ v,
     }
     __syncthreads();
   }
+}
+
+// Shapelet sources, added into the coherencies k_predict_coh has written
+// (launched after it on the same stream; k_predict_coh sees their fluxes
+// zeroed). One thread per row; the loop over the S table entries is
+// block-uniform, so parameters, coefficients and recurrence constants are
+// uniform loads. Entries are sorted by source index (cluster ids
+// non-decreasing): Stokes sums stay in registers while the cluster id
+// repeats and are added to out[ci, r, :] on a change — each (ci, r)
+// belongs to one thread, so the sums need no atomics.
+//
+// Envelope of entry s at wavelength-scaled (u,v,w) (shapelet.c:141-188):
+//   up = psign (u cxi - v cphi sxi + w sphi sxi)   psign = -1 projected,
+//   vp = psign (u sxi + v cphi cxi - w sphi cxi)   else +1 with identity
+//   ut = a (ceP up - seP vp),  vt = b (seP up + ceP vp)
+//   env = sum_{n1,n2} coef[n2 n0 + n1] phi_n1(-ut beta) phi_n2(vt beta)
+// taken as real for even n1+n2 and imaginary for odd; the i^(n1+n2) sign
+// and 2 pi a b are folded into coef on the host. phi_n is the normalised
+// Hermite function, phi_0 = e^{-x^2/2}/sqrt(2), phi_n = x sqrt(2/n)
+// phi_{n-1} - sqrt((n-1)/n) phi_{n-2}; rec holds the two constants per n.
+extern "C" __global__ void __launch_bounds__(128)
+k_shapelet_coh(const double* __restrict__ u, const double* __restrict__ v,
+               const double* __restrict__ w, int R, int S,
+               const int* __restrict__ src, const int* __restrict__ cluster,
+               const int* __restrict__ n0t, const float* __restrict__ betat,
+               const int* __restrict__ off, const float* __restrict__ coef,
+               const float* __restrict__ cxi, const float* __restrict__ sxi,
+               const float* __restrict__ cphi, const float* __restrict__ sphi,
+               const float* __restrict__ psign, const float* __restrict__ at,
+               const float* __restrict__ bt, const float* __restrict__ ceP,
+               const float* __restrict__ seP,
+               const double* __restrict__ ll, const double* __restrict__ mm,
+               const double* __restrict__ nn1,
+               const float* __restrict__ rec, int nmax,  // [2, nmax]
+               const float* __restrict__ flux,           // [4, S] I,Q,U,V
+               const float* __restrict__ r1t,            // [S]
+               double freq, double fdelta2, double tdelta,
+               const float* __restrict__ beam,   // [T, K, N] or null
+               const int* __restrict__ pairs,    // [Nbase, 2] (with beam)
+               int Nbase, int Ktot, int Nsta,
+               float2* out) {                    // [M, R, 4], added into
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  int b_sta1 = 0, b_sta2 = 0;
+  size_t b_toff = 0;
+  if (beam != nullptr) {
+    const int t = r / Nbase, bl = r - t * Nbase;
+    b_sta1 = pairs[2 * bl];
+    b_sta2 = pairs[2 * bl + 1];
+    b_toff = (size_t)t * Ktot;
+  }
+  const double ur = u[r], vr = v[r], wr = w[r];
+  const float blf = (float)(sqrt(ur * ur + vr * vr + wr * wr) * freq);
+  const float uf = (float)(ur * freq), vf = (float)(vr * freq),
+              wf = (float)(wr * freq);
+  const float tsm_c = 7.2921150e-5f * (float)tdelta * blf;
+  const float* rec0 = rec;          // sqrt(2/n)
+  const float* rec1 = rec + nmax;   // sqrt((n-1)/n)
+
+  cf aI = {0.f, 0.f}, aQ = {0.f, 0.f}, aU = {0.f, 0.f}, aV = {0.f, 0.f};
+  auto flush = [&](int ci) {
+    // Stokes -> coherency [[I+Q, U+jV],[U-jV, I-Q]] (predict.c:228-235)
+    float2* o = out + ((size_t)ci * R + r) * 4;
+    o[0] = cadd(o[0], cadd(aI, aQ));
+    o[1] = cadd(o[1], {aU.x - aV.y, aU.y + aV.x});
+    o[2] = cadd(o[2], {aU.x + aV.y, aU.y - aV.x});
+    o[3] = cadd(o[3], csub(aI, aQ));
+  };
+  int cur = cluster[0];
+  for (int s = 0; s < S; ++s) {
+    const int ci = cluster[s];
+    if (ci != cur) {
+      flush(cur);
+      aI = {0.f, 0.f}; aQ = {0.f, 0.f}; aU = {0.f, 0.f}; aV = {0.f, 0.f};
+      cur = ci;
+    }
+    cf phc = phase_smear(ur, vr, wr, ll[s], mm[s], nn1[s], freq, fdelta2,
+                         tsm_c, r1t[s]);
+    const float c_xi = cxi[s], s_xi = sxi[s];
+    const float c_ph = cphi[s], s_ph = sphi[s];
+    const float up = psign[s] *
+        (uf * c_xi - vf * c_ph * s_xi + wf * s_ph * s_xi);
+    const float vp = psign[s] *
+        (uf * s_xi + vf * c_ph * c_xi - wf * s_ph * c_xi);
+    const float ut = at[s] * (ceP[s] * up - seP[s] * vp);
+    const float vt = bt[s] * (seP[s] * up + ceP[s] * vp);
+    const float beta = betat[s];
+    const float xu = -ut * beta, xv = vt * beta;
+    const float pu0 = 0.70710678118654752f * expf(-0.5f * xu * xu);
+    const int n0 = n0t[s];
+    const float* cf_s = coef + off[s];
+    float re = 0.f, im = 0.f;
+    float pv1 = 0.f, pv = 0.70710678118654752f * expf(-0.5f * xv * xv);
+    for (int n2 = 0; n2 < n0; ++n2) {
+      if (n2 > 0) {
+        const float t = xv * rec0[n2] * pv - rec1[n2] * pv1;
+        pv1 = pv;
+        pv = t;
+      }
+      // row sums over even and odd n1
+      float se = 0.f, so = 0.f;
+      float pu1 = 0.f, pu = pu0;
+      const float* c = cf_s + n2 * n0;
+      for (int n1 = 0; n1 < n0; ++n1) {
+        if (n1 > 0) {
+          const float t = xu * rec0[n1] * pu - rec1[n1] * pu1;
+          pu1 = pu;
+          pu = t;
+        }
+        if (n1 & 1) so += c[n1] * pu;
+        else        se += c[n1] * pu;
+      }
+      if (n2 & 1) { re += pv * so; im += pv * se; }
+      else        { re += pv * se; im += pv * so; }
+    }
+    phc = cmul(phc, {re, im});
+    if (beam != nullptr) {
+      const float* bg = beam + (b_toff + (size_t)src[s]) * (size_t)Nsta;
+      phc = cscale(phc, bg[b_sta1] * bg[b_sta2]);
+    }
+    aI = cadd(aI, cscale(phc, flux[s]));
+    aQ = cadd(aQ, cscale(phc, flux[S + s]));
+    aU = cadd(aU, cscale(phc, flux[2 * S + s]));
+    aV = cadd(aV, cscale(phc, flux[3 * S + s]));
+  }
+  flush(cur);
 }

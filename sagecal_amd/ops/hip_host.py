@@ -2,8 +2,9 @@
 
 Handles layout preparation: per-frequency flux scaling (done with torch on
 device, keeping the predict kernel free of spectral-index math), baking the
-projection identity into unused rotation terms, chunk tables, station-pair
-index tables, and complex64 views.
+projection identity into unused rotation terms, the device-resident
+shapelet mode table, chunk tables, station-pair index tables, and
+complex64 views.
 """
 import math
 import os
@@ -21,6 +22,170 @@ def _ext():
         raise RuntimeError(
             f"dirac_hip extension unavailable: {dispatch._ext_err}")
     return e
+
+
+class ShapeletTable:
+    """Device-resident table of the pack's shapelet sources, read by
+    k_shapelet_coh and by shapelet_coh_torch. Built once from the host-side
+    `pack.shapelets` dict; S entries sorted by global source index, so
+    cluster ids are non-decreasing.
+
+      src, cluster, n0   int32 [S]    global source / cluster index, order
+      beta               float [S]    shapelet scale
+      off                int32 [S+1]  prefix sum of n0^2
+      coef               float [off[S]]  mode (n1,n2) of entry s at
+                         off[s] + n2*n0 + n1, holding
+                         modes[n2*n0+n1] * sgn(n1+n2) * 2 pi a b with
+                         sgn(k) = +1 for k mod 4 in {0,1}, else -1: the
+                         mode value is i^(n1+n2) phi_n1 phi_n2, so the
+                         parity of n1+n2 alone picks the real or the
+                         imaginary accumulator
+      cxi,sxi,cphi,sphi  float [S]    projection rotation, identity
+                         (1,0,1,0) when the source's use_proj is off
+      psign              float [S]    -1 with use_proj (the shapelet
+                         projection is the NEGATED gaussian one,
+                         shapelet.shapelet_contrib), else +1
+      a, b, ceP, seP     float [S]    1/eX, 1/eY, cos(eP), sin(eP)
+      ll, mm, nn1        float64 [S]  direction cosines
+      rec                float [2, max n0]  recurrence constants
+                         sqrt(2/n), sqrt((n-1)/n); rec[:,0] unused
+
+    `float` is float32, the kernel's layout; dtype=torch.float64 keeps the
+    host-computed values unrounded for fp64 checks of the mirror. The
+    main-kernel rotation arrays of GPUPack bake use_proj | stype>=2, which
+    is wrong for shapelets, so the table bakes its own."""
+
+    FIELDS = ('src', 'cluster', 'n0', 'beta', 'off', 'coef', 'cxi', 'sxi',
+              'cphi', 'sphi', 'psign', 'a', 'b', 'ceP', 'seP', 'll', 'mm',
+              'nn1', 'rec')
+
+    def __init__(self, pack, device, dtype=torch.float32):
+        import numpy as np
+        items = sorted(pack.shapelets.items())
+        src = np.array([g for g, _ in items], dtype=np.int64)
+        host = lambda t: t.detach().cpu().to(torch.float64).numpy()[src]
+        co = pack.cluster_off.detach().cpu().numpy()
+        n0 = np.array([sh[0] for _, sh in items], dtype=np.int64)
+        off = np.concatenate([[0], np.cumsum(n0 * n0)])
+        proj = pack.use_proj.detach().cpu().numpy()[src] != 0
+        a, b = 1.0 / host(pack.eX), 1.0 / host(pack.eY)
+        eP = host(pack.eP)
+        coef = np.zeros(int(off[-1]))
+        for s, (_, (n, _beta, modes)) in enumerate(items):
+            k = np.arange(n)
+            nsum = k[None, :] + k[:, None]               # [n2, n1]
+            sgn = np.where(nsum % 4 < 2, 1.0, -1.0)
+            m = np.asarray(modes, dtype=np.float64).reshape(n, n)
+            coef[off[s]:off[s + 1]] = (
+                m * sgn * (2.0 * math.pi * a[s] * b[s])).reshape(-1)
+        self.nmax = int(n0.max())
+        rec = np.zeros((2, self.nmax))
+        k = np.arange(1, self.nmax)
+        rec[0, 1:] = np.sqrt(2.0 / k)
+        rec[1, 1:] = np.sqrt((k - 1.0) / k)
+        # dense [S, n2, n1] view of coef for the torch mirror: index into
+        # coef, or one past its end (a zero slot) beyond the entry's order
+        k = np.arange(self.nmax)
+        idx = off[:-1, None, None] + k[None, :, None] * n0[:, None, None] \
+            + k[None, None, :]
+        inside = (k[None, :, None] < n0[:, None, None]) & \
+            (k[None, None, :] < n0[:, None, None])
+        self.S = len(items)
+        self.M = int(pack.M)
+        self.K = int(pack.K) if hasattr(pack, 'K') else int(co[-1])
+        i32 = lambda x: torch.as_tensor(
+            np.ascontiguousarray(x), dtype=torch.int32).to(device)
+        flt = lambda x, dt=dtype: torch.as_tensor(
+            np.ascontiguousarray(x), dtype=torch.float64).to(
+                device=device, dtype=dt).contiguous()
+        self.src = i32(src)
+        self.cluster = i32(np.searchsorted(co, src, side='right') - 1)
+        self.n0 = i32(n0)
+        self.off = i32(off)
+        self.beta = flt([sh[1] for _, sh in items])
+        self.coef = flt(coef)
+        self.cxi = flt(np.where(proj, host(pack.cxi), 1.0))
+        self.sxi = flt(np.where(proj, host(pack.sxi), 0.0))
+        self.cphi = flt(np.where(proj, host(pack.cphi), 1.0))
+        self.sphi = flt(np.where(proj, host(pack.sphi), 0.0))
+        self.psign = flt(np.where(proj, -1.0, 1.0))
+        self.a, self.b = flt(a), flt(b)
+        self.ceP, self.seP = flt(np.cos(eP)), flt(np.sin(eP))
+        self.ll = flt(host(pack.ll), torch.float64)
+        self.mm = flt(host(pack.mm), torch.float64)
+        self.nn1 = flt(host(pack.nn1), torch.float64)
+        self.rec = flt(rec)
+        self.cluster_long = self.cluster.long()
+        self.src_long = self.src.long()
+        self.pad_idx = torch.as_tensor(
+            np.where(inside, idx, int(off[-1]))).to(device)
+
+
+def shapelet_coh_torch(tab, flux, r1, u, v, w, freq, fdelta, tdelta,
+                       beam=None, pairs=None, Nbase=0):
+    """Vectorised torch mirror of k_shapelet_coh over [B, S]: coherencies
+    [M, B, 2, 2] of the table's shapelet sources only, on the device and in
+    the real dtype of `u`, with no host synchronisation. flux: [4, S]
+    I,Q,U,V at the channel; r1: [S] time-smear distance term; optional
+    beam [T, K, N] and pairs [Nbase, 2] as in predict_coh."""
+    rt = u.dtype
+    c = lambda t: t.to(rt)
+    uc, vc, wc = u[:, None], v[:, None], w[:, None]
+    two_pi = 2.0 * math.pi
+    G = two_pi * (uc * c(tab.ll) + vc * c(tab.mm) + wc * c(tab.nn1))
+    ph = torch.fmod(G * freq, two_pi)
+    smf = G * (fdelta * 0.5)
+    big = smf.abs() > 1e-9
+    sm = torch.where(big, (torch.sin(smf)
+                           / torch.where(big, smf, torch.ones_like(smf))
+                           ).abs(), torch.ones_like(smf))
+    blf = torch.sqrt(uc * uc + vc * vc + wc * wc) * freq
+    prod = (7.2921150e-5 * float(tdelta)) * blf * c(r1)
+    sm = sm * torch.where(prod > 1e-9, 1.0645 * torch.erf(0.8326 * prod)
+                          / prod.clamp_min(1e-9), torch.ones_like(prod))
+    phc = torch.complex(torch.cos(ph) * sm, torch.sin(ph) * sm)
+    uf, vf, wf = uc * freq, vc * freq, wc * freq
+    cxi, sxi = c(tab.cxi), c(tab.sxi)
+    cphi, sphi = c(tab.cphi), c(tab.sphi)
+    up = c(tab.psign) * (uf * cxi - vf * cphi * sxi + wf * sphi * sxi)
+    vp = c(tab.psign) * (uf * sxi + vf * cphi * cxi - wf * sphi * cxi)
+    ut = c(tab.a) * (c(tab.ceP) * up - c(tab.seP) * vp)
+    vt = c(tab.b) * (c(tab.seP) * up + c(tab.ceP) * vp)
+    beta = c(tab.beta)
+    rec = c(tab.rec)
+
+    def phi(x):                       # [B, S] -> [B, S, nmax]
+        cols = [math.sqrt(0.5) * torch.exp(-0.5 * x * x)]
+        prev = torch.zeros_like(x)
+        for n in range(1, tab.nmax):
+            cols.append(x * rec[0, n] * cols[-1] - rec[1, n] * prev)
+            prev = cols[-2]
+        return torch.stack(cols, dim=-1)
+    pu, pv = phi(-ut * beta), phi(vt * beta)
+    coef = torch.cat([c(tab.coef), torch.zeros(1, dtype=rt,
+                                               device=u.device)])
+    cd = coef[tab.pad_idx]                                   # [S, n2, n1]
+    k = torch.arange(tab.nmax, device=u.device)
+    odd = ((k[:, None] + k[None, :]) % 2 == 1).to(rt)
+    re = torch.einsum('bsk,skl,bsl->bs', pv, cd * (1.0 - odd), pu)
+    im = torch.einsum('bsk,skl,bsl->bs', pv, cd * odd, pu)
+    term = phc * torch.complex(re, im)
+    if beam is not None:
+        B = u.shape[0]
+        Nbase = int(Nbase) or int(pairs.shape[0])
+        row = torch.arange(B, device=u.device)
+        t, bl = row // Nbase, row % Nbase
+        p, q = pairs[bl, 0].long(), pairs[bl, 1].long()
+        g = tab.src_long[None, :]
+        term = term * c(beam[t[:, None], g, p[:, None]]
+                        * beam[t[:, None], g, q[:, None]])
+    fI, fQ, fU, fV = (term * c(flux[i]) for i in range(4))
+    coh = torch.stack([fI + fQ, fU + 1j * fV, fU - 1j * fV, fI - fQ],
+                      dim=-1)                                # [B, S, 4]
+    out = torch.zeros(tab.M, u.shape[0], 4, dtype=coh.dtype,
+                      device=u.device)
+    out.index_add_(0, tab.cluster_long, coh.permute(1, 0, 2).contiguous())
+    return out.view(tab.M, -1, 2, 2)
 
 
 class GPUPack:
@@ -48,18 +213,21 @@ class GPUPack:
         self.sphi = torch.where(up, f32(pack.sphi), zero).contiguous()
         self.stype = pack.stype.to(device=device,
                                    dtype=torch.int32).contiguous()
-        # shapelet sources are handled by the torch path (shapelet.py):
-        # zero their fluxes for the kernel so they contribute nothing there
-        self.shapelets = dict(getattr(pack, 'shapelets', {}))
-        if self.shapelets:
-            # keep the true fluxes for the host shapelet pass, zero them
-            # in the kernel arrays
+        # shapelet sources go through k_shapelet_coh from the table below:
+        # zero their fluxes in the main-kernel arrays so they contribute
+        # nothing there, and keep the true ones gathered per table entry
+        self.sh = None
+        if getattr(pack, 'shapelets', None):
+            self.sh = ShapeletTable(pack, device)
+            src = self.sh.src
+            gather = lambda ks: torch.stack(
+                [getattr(self, k).index_select(0, src) for k in ks]
+            ).contiguous()
+            self._sh_flux = gather(('sI', 'sQ', 'sU', 'sV'))        # [4,S]
+            self._sh_flux0 = gather(('sI0', 'sQ0', 'sU0', 'sV0'))
             sh = self.stype == 4
-            self._shfull = {}
             for k in ('sI', 'sQ', 'sU', 'sV', 'sI0', 'sQ0', 'sU0', 'sV0'):
-                t = getattr(self, k)
-                self._shfull[k] = t.clone()
-                t = t.clone()
+                t = getattr(self, k).clone()
                 t[sh] = 0.0
                 setattr(self, k, t.contiguous())
         self.pack_ref = pack
@@ -68,30 +236,50 @@ class GPUPack:
                                                dtype=torch.int32).contiguous()
         self.freq0 = None
         self._flux_cache = {}
+        self._sh_flux_cache = {}
+
+    def _flog(self, freq):
+        """Log-polynomial spectral exponent per source at `freq`."""
+        lf = torch.log(torch.tensor(float(freq), dtype=torch.float64,
+                                    device=self.ll.device) / self.f0)
+        lf = lf.to(torch.float32)
+        return (self.spec_idx * lf + self.spec_idx1 * lf ** 2
+                + self.spec_idx2 * lf ** 3)
+
+    @staticmethod
+    def _scale(s0, flog):
+        mag = torch.exp(torch.log(s0.abs().clamp_min(1e-30)) + flog)
+        return torch.where(s0 == 0, torch.zeros_like(s0),
+                           torch.sign(s0) * mag)
 
     def fluxes_at(self, freq, freq0):
         """Per-source fluxes at channel `freq`; pack fluxes are given at
-        freq0 (sI..) and catalogue f0 (sI0..)."""
+        freq0 (sI..) and catalogue f0 (sI0..). Shapelet sources are zero
+        here; their fluxes at the same channel are cached alongside
+        (shapelet_fluxes_at)."""
         key = round(float(freq), 3)
         if key in self._flux_cache:
             return self._flux_cache[key]
         if abs(freq - freq0) < 1.0:
             out = (self.sI, self.sQ, self.sU, self.sV)
+            if self.sh is not None:
+                self._sh_flux_cache[key] = self._sh_flux
         else:
-            lf = torch.log(torch.tensor(float(freq), dtype=torch.float64,
-                                        device=self.ll.device) / self.f0)
-            lf = lf.to(torch.float32)
-            flog = (self.spec_idx * lf + self.spec_idx1 * lf ** 2
-                    + self.spec_idx2 * lf ** 3)
-
-            def scale(s0):
-                mag = torch.exp(torch.log(s0.abs().clamp_min(1e-30)) + flog)
-                return torch.where(s0 == 0, torch.zeros_like(s0),
-                                   torch.sign(s0) * mag)
-            out = (scale(self.sI0), scale(self.sQ0), scale(self.sU0),
-                   scale(self.sV0))
+            flog = self._flog(freq)
+            out = tuple(self._scale(s0, flog) for s0 in
+                        (self.sI0, self.sQ0, self.sU0, self.sV0))
+            if self.sh is not None:
+                self._sh_flux_cache[key] = self._scale(
+                    self._sh_flux0,
+                    flog.index_select(0, self.sh.src)).contiguous()
         self._flux_cache[key] = out
         return out
+
+    def shapelet_fluxes_at(self, freq, freq0):
+        """Un-zeroed I, Q, U, V of the shapelet sources at channel `freq`,
+        [4, S] float32 in table order."""
+        self.fluxes_at(freq, freq0)
+        return self._sh_flux_cache[round(float(freq), 3)]
 
     def r1_for(self, dec0):
         """Time-smear source-distance term sqrt(ll^2+(sin(dec0) mm)^2)
@@ -119,7 +307,11 @@ def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
     (-B 1, reference DOBEAM_ARRAY): `beam` [T, K, N] float32 real
     array-factor gains on device + `pairs` [Nbase, 2] int32 — each
     source's contribution is scaled by beam[t,k,p]*beam[t,k,q] inside
-    k_predict_coh (predict_model.cu:843-852 semantics)."""
+    k_predict_coh (predict_model.cu:843-852 semantics). Shapelet sources
+    (gp.sh) are added by k_shapelet_coh on the same stream, beam-scaled
+    the same way; once the pack is on the device this path has no host
+    synchronisation. SAGECAL_SHAPELET_HOST=1 swaps that kernel for its
+    torch mirror shapelet_coh_torch."""
     gp = pack if isinstance(pack, GPUPack) else gpu_pack(pack, u.device)
     sI, sQ, sU, sV = gp.fluxes_at(freq, freq0)
     r1 = gp.r1_for(dec0)
@@ -135,73 +327,24 @@ def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
         gp.eX, gp.eY, gp.eP, gp.cxi, gp.sxi, gp.cphi, gp.sphi, r1,
         gp.stype, gp.cluster_off, float(freq), float(fdelta) * 0.5,
         float(tdelta), beam=beam, pairs=pairs, Nbase=int(Nbase))
-    out = out.view(gp.M, -1, 2, 2)
-    if gp.shapelets:
-        out = out + _shapelet_coh(gp, u64, v64, w64, freq, freq0, fdelta,
-                                  tdelta, dec0).to(out.dtype)
-    return out
-
-
-def _shapelet_coh(gp, u, v, w, freq, freq0, fdelta, tdelta, dec0):
-    """Additive coherency of shapelet sources, computed with torch on
-    device (mirrors reference.predict_coh for stype==4 sources only)."""
-    from .. import shapelet as shmod
-    import numpy as np
-    M = gp.M
-    B = u.shape[0]
-    out = torch.zeros(M, B, 2, 2, dtype=torch.complex64, device=u.device)
-    co = gp.cluster_off.cpu().numpy()
-    pk = gp.pack_ref
-    # true (un-zeroed) fluxes at this channel
-    full = gp._shfull
-    if abs(freq - freq0) < 1.0:
-        sIs, sQs, sUs, sVs = (full['sI'], full['sQ'], full['sU'],
-                              full['sV'])
-    else:
-        lf = torch.log(torch.tensor(float(freq), dtype=torch.float64,
-                                    device=gp.ll.device) / gp.f0)
-        lf = lf.to(torch.float32)
-        flog = (gp.spec_idx * lf + gp.spec_idx1 * lf ** 2
-                + gp.spec_idx2 * lf ** 3)
-
-        def _scale(s0):
-            mag = torch.exp(torch.log(s0.abs().clamp_min(1e-30)) + flog)
-            return torch.where(s0 == 0, torch.zeros_like(s0),
-                               torch.sign(s0) * mag)
-        sIs, sQs, sUs, sVs = (_scale(full['sI0']), _scale(full['sQ0']),
-                              _scale(full['sU0']), _scale(full['sV0']))
-    for gi, (n0, beta, modes) in gp.shapelets.items():
-        ci = int(np.searchsorted(co, gi, side='right') - 1)
-        ll = float(gp.ll[gi]); mm = float(gp.mm[gi]); nn1 = float(gp.nn1[gi])
-        G = 2.0 * math.pi * (u * ll + v * mm + w * nn1)
-        ph = torch.remainder(G * freq, 2.0 * math.pi)
-        phc = torch.complex(torch.cos(ph), torch.sin(ph))
-        smf = G * (fdelta * 0.5)
-        sm = torch.where(smf.abs() > 1e-12,
-                         (torch.sin(smf) / smf).abs(),
-                         torch.ones_like(smf))
-        if tdelta > 0:
-            bl = torch.sqrt(u * u + v * v + w * w) * freq
-            r1 = math.sqrt(ll * ll + (math.sin(dec0) * mm) ** 2)
-            prod = 7.2921150e-5 * tdelta * bl * r1
-            sm = sm * torch.where(prod > 1e-12,
-                                  1.0645 * torch.erf(0.8326 * prod)
-                                  / prod.clamp_min(1e-12),
-                                  torch.ones_like(prod))
-        envc = shmod.shapelet_contrib(
-            u * freq, v * freq, w * freq, float(gp.eX[gi]),
-            float(gp.eY[gi]), float(gp.eP[gi]), float(pk.cxi[gi]),
-            float(pk.sxi[gi]), float(pk.cphi[gi]), float(pk.sphi[gi]),
-            bool(pk.use_proj[gi]), beta, n0, torch.as_tensor(modes))
-        term = (phc * sm.to(phc.dtype) * envc).to(torch.complex64)
-        # note: use_proj baked as identity when off; contrib uses proj form
-        I = float(sIs[gi]); Q = float(sQs[gi])
-        U_ = float(sUs[gi]); V_ = float(sVs[gi])
-        out[ci, :, 0, 0] += term * (I + Q)
-        out[ci, :, 0, 1] += term * complex(U_, V_)
-        out[ci, :, 1, 0] += term * complex(U_, -V_)
-        out[ci, :, 1, 1] += term * (I - Q)
-    return out
+    if gp.sh is not None:
+        tab = gp.sh
+        flux = gp.shapelet_fluxes_at(freq, freq0)
+        r1s = r1.index_select(0, tab.src)
+        if beam is not None and beam.shape[1] < tab.K:
+            raise ValueError("beam covers fewer sources than the pack")
+        if os.environ.get('SAGECAL_SHAPELET_HOST') == '1':
+            # torch mirror of the kernel (same table), for cross-checks
+            add = shapelet_coh_torch(tab, flux, r1s, u64, v64, w64,
+                                     float(freq), float(fdelta),
+                                     float(tdelta), beam, pairs, Nbase)
+            out = out + add.reshape(gp.M, -1, 4).to(out.dtype)
+        else:
+            _ext().shapelet_coh_add(
+                out, u64, v64, w64, *(getattr(tab, k) for k in tab.FIELDS),
+                flux, r1s, float(freq), float(fdelta) * 0.5, float(tdelta),
+                beam=beam, pairs=pairs, Nbase=int(Nbase))
+    return out.view(gp.M, -1, 2, 2)
 
 
 class BaselineLayout:

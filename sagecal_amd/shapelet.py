@@ -11,13 +11,15 @@ Re-implements /root/reference/src/lib/Radio/shapelet.c:
   - read_shapelet_modes (readsky.c:149-190): `<name>.fits.modes` text file
     (RA/Dec line, then n0 beta, then n0^2 `idx value` rows).
 
-Vectorized torch (runs on CPU or GPU tensors); the HIP predict kernel
-leaves shapelet sources to this path (their fluxes are zeroed in the
-kernel pack and their contribution is added by the host — sources per
-cluster are few while baselines are many, so the torch pass is cheap).
-The device-side malloc + recursive Hermite of the reference's CUDA path
-(predict_model.cu:708-784) is replaced by closed-loop recurrences on
-tensors (SURVEY.md §7 "shapelets" hard-part note).
+Vectorized torch (runs on CPU or GPU tensors): this is the CPU and
+reference path. On the GPU the predict does not come here: shapelet
+sources are evaluated by the HIP kernel k_shapelet_coh
+(ops/hip/predict.hip) from the device-resident table
+ops.hip_host.ShapeletTable, whose torch mirror is
+ops.hip_host.shapelet_coh_torch. The device-side malloc + recursive
+Hermite of the reference's CUDA path (predict_model.cu:708-784) is
+replaced by closed-loop recurrences, on tensors here and in registers in
+the kernel (SURVEY.md §7 "shapelets" hard-part note).
 """
 import math
 
