@@ -24,7 +24,7 @@ hipError_t launch_jtj_accum(const float2*, const float2*, const float2*,
     int, float2*, float2*, float*, int*, float2*, float2*, float2*, float*,
     int, int, hipStream_t);
 hipError_t launch_jtj_expand(const float2*, const float2*, const float2*,
-    const int*, int, int, int, float*, float*, hipStream_t);
+    const int*, const int*, int, int, int, float*, float*, hipStream_t);
 hipError_t launch_model_cost(const float2*, const float2*, const float2*,
     const int*, const int*, const float*, int, int, int, int, int, float*,
     float*, hipStream_t);
@@ -202,7 +202,8 @@ std::vector<torch::Tensor> jtj_jtr(
   auto JtJ = torch::empty({Mt, 8 * N, 8 * N}, fopts);
   auto Jtr = torch::empty({Mt, 8 * N}, fopts);
   CHECK_HIP(launch_jtj_expand(ccptr(D), ccptr(g), ccptr(Cx),
-      pidx.data_ptr<int>(), (int)N, (int)npair, (int)Mt,
+      pairs.data_ptr<int>(), pidx.data_ptr<int>(), (int)N, (int)npair,
+      (int)Mt,
       JtJ.data_ptr<float>(), Jtr.data_ptr<float>(), cur_stream()));
   return {JtJ, Jtr, cost};
 }

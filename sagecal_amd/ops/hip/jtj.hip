@@ -216,9 +216,14 @@ k_jtj_reduce(const float2* __restrict__ PD, const float2* __restrict__ Pg,
 
 // Expand accumulators into the dense JtJ [Mt, 8N, 8N] + Jtr [Mt, 8N].
 // One 64-thread block per (chunk, s1, s2) 8x8 block; thread per entry.
+// k_jtj_accum stored the cross block of pair pi with rows = parameters of
+// station pairs[2*pi] and columns = those of pairs[2*pi+1], whichever of
+// the two has the lower number: block (s1, s2) takes it as stored when s1
+// is the pair's first station and transposed when it is the second.
 extern "C" __global__ void __launch_bounds__(64)
 k_jtj_expand(const float2* __restrict__ D, const float2* __restrict__ g,
              const float2* __restrict__ Cx,
+             const int* __restrict__ pairs,  // [npair_slots*2]
              const int* __restrict__ pidx,   // [N*N] pair index or -1
              int N, int npair_slots,
              float* __restrict__ JtJ, float* __restrict__ Jtr) {
@@ -230,10 +235,13 @@ k_jtj_expand(const float2* __restrict__ D, const float2* __restrict__ g,
   const size_t P = (size_t)8 * N;
   float val = 0.f;
   if (s1 == s2) {
-    // I2 (x) realify(A): block diag 4x4 repeated
+    // I2 (x) realify(A): block diag 4x4 repeated. A is Hermitian only to
+    // rounding (its diagonal carries an imaginary residue, A[1] is not
+    // bitwise conj(A[2])), so the entries above the diagonal mirror the
+    // ones below, which the Cholesky kernels read: JtJ == JtJ^T exactly
     if ((row >> 2) == (col >> 2)) {
       const cf* A = D + ((size_t)c * N + s1) * 4;
-      const int r4 = row & 3, c4 = col & 3;
+      const int r4 = max(row, col) & 3, c4 = min(row, col) & 3;
       const cf a = A[(r4 >> 1) * 2 + (c4 >> 1)];
       // realify: [[ar,-ai],[ai,ar]]
       val = ((r4 & 1) == 0) ? (((c4 & 1) == 0) ? a.x : -a.y)
@@ -246,17 +254,21 @@ k_jtj_expand(const float2* __restrict__ D, const float2* __restrict__ g,
       Jtr[(size_t)c * P + 8 * s1 + e] = (e & 1) ? gv.y : gv.x;
     }
   } else {
-    const bool upper = s1 < s2;
-    const int a_ = upper ? s1 : s2, b_ = upper ? s2 : s1;
-    const int pi = pidx[a_ * N + b_];
-    if (pi >= 0) {
-      const cf* X = Cx + ((size_t)c * npair_slots + pi) * 16;
-      // antirealify: entry ((ij),(kb)) complex v -> [[vx,vy],[vy,-vx]]
-      int rr = row, cc = col;
-      if (!upper) { rr = col; cc = row; }   // transpose block
-      const cf v2 = X[(rr >> 1) * 4 + (cc >> 1)];
-      val = ((rr & 1) == 0) ? (((cc & 1) == 0) ? v2.x : v2.y)
-                            : (((cc & 1) == 0) ? v2.y : -v2.x);
+    const int lo = min(s1, s2), hi = max(s1, s2);
+    const int pi = pidx[lo * N + hi];
+    if (pi >= 0 && pi < npair_slots) {
+      const int first = pairs[2 * pi], second = pairs[2 * pi + 1];
+      // a pair flagged in this layout (or a table of another layout)
+      // names neither station: the block stays zero
+      if ((first == s1 && second == s2) || (first == s2 && second == s1)) {
+        const cf* X = Cx + ((size_t)c * npair_slots + pi) * 16;
+        // antirealify: entry ((ij),(kb)) complex v -> [[vx,vy],[vy,-vx]]
+        int rr = row, cc = col;
+        if (first != s1) { rr = col; cc = row; }   // transpose block
+        const cf v2 = X[(rr >> 1) * 4 + (cc >> 1)];
+        val = ((rr & 1) == 0) ? (((cc & 1) == 0) ? v2.x : v2.y)
+                              : (((cc & 1) == 0) ? v2.y : -v2.x);
+      }
     }
   }
   JtJ[(size_t)c * P * P + ((size_t)8 * s1 + row) * P + 8 * s2 + col] = val;

@@ -64,10 +64,11 @@ hipError_t launch_jtj_accum(
 }
 
 hipError_t launch_jtj_expand(
-    const float2* D, const float2* g, const float2* Cx, const int* pidx,
-    int N, int npair, int Mt, float* JtJ, float* Jtr, hipStream_t stream) {
+    const float2* D, const float2* g, const float2* Cx, const int* pairs,
+    const int* pidx, int N, int npair, int Mt, float* JtJ, float* Jtr,
+    hipStream_t stream) {
   hipLaunchKernelGGL(k_jtj_expand, dim3(N, N, Mt), dim3(64), 0, stream,
-      D, g, Cx, pidx, N, npair, JtJ, Jtr);
+      D, g, Cx, pairs, pidx, N, npair, JtJ, Jtr);
   return hipGetLastError();
 }
 

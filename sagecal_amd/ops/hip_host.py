@@ -13,7 +13,8 @@ import torch
 
 from . import dispatch
 
-_pidx_cache = {}
+_pidx_cache = {}     # (N, Nbase, device) -> (host table, device table)
+_layout_memo = {}    # (bb token, version, Nbase, N, device) -> (pairs, pidx)
 
 
 def _ext():
@@ -350,22 +351,51 @@ def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
 class BaselineLayout:
     """Row-structure descriptor for the solver kernels: rows are
     seg*(T*Nbase) + t*Nbase + b with a fixed pair table. Built once per
-    tile; pair-index table cached per (N, Nbase)."""
+    tile. pairs[b] = (p, q) as the data stores them, in any order and
+    with either station first; pidx[min(p,q), max(p,q)] = b.
+
+    The pair-index table is cached per (N, Nbase, device) and reused only
+    by a layout that agrees with it on every unflagged pair, so a table
+    that differs from the cached one by flagged (-1) rows alone shares it
+    (the kernels skip those slots through `pairs`); any other pair order
+    gets a table of its own, which takes the cache slot. The comparison
+    reads the pair table back to the host, so its outcome is remembered
+    per bb tensor: building the layout of the same rows again, as
+    lbfgs_cost_grad does on every call, costs no synchronisation."""
 
     def __init__(self, bb, Nbase, T, nseg, N, device):
         self.Nbase, self.T, self.nseg, self.N = Nbase, T, nseg, N
-        self.pairs = bb[:Nbase].to(device=device,
-                                   dtype=torch.int32).contiguous()
+        try:
+            mkey = (dispatch.obj_token(bb), bb._version, Nbase, N,
+                    str(device))
+        except RuntimeError:             # inference tensor: no version
+            mkey = None
+        hit = _layout_memo.get(mkey)
+        if hit is None:
+            pairs = bb[:Nbase].to(device=device,
+                                  dtype=torch.int32).contiguous()
+            hit = (pairs, self._pidx_for(pairs, Nbase, N, device))
+            if mkey is not None:
+                if len(_layout_memo) > 64:   # bound long multi-MS runs
+                    _layout_memo.pop(next(iter(_layout_memo)))
+                _layout_memo[mkey] = hit
+        self.pairs, self.pidx = hit
+
+    @staticmethod
+    def _pidx_for(pairs, Nbase, N, device):
+        pcpu = pairs.cpu().long()
+        ok = (pcpu[:, 0] >= 0) & (pcpu[:, 1] >= 0)
+        lo = torch.minimum(pcpu[:, 0], pcpu[:, 1])[ok]
+        hi = torch.maximum(pcpu[:, 0], pcpu[:, 1])[ok]
+        b = torch.arange(Nbase, dtype=torch.int32)[ok]
         key = (N, Nbase, str(device))
-        if key not in _pidx_cache:
-            pidx = torch.full((N, N), -1, dtype=torch.int32)
-            pcpu = self.pairs.cpu().long()
-            ok = (pcpu[:, 0] >= 0) & (pcpu[:, 1] >= 0)
-            lo = torch.minimum(pcpu[:, 0], pcpu[:, 1])[ok]
-            hi = torch.maximum(pcpu[:, 0], pcpu[:, 1])[ok]
-            pidx[lo, hi] = torch.arange(Nbase, dtype=torch.int32)[ok]
-            _pidx_cache[key] = pidx.to(device).contiguous()
-        self.pidx = _pidx_cache[key]
+        cached = _pidx_cache.get(key)
+        if cached is not None and bool((cached[0][lo, hi] == b).all()):
+            return cached[1]
+        pidx = torch.full((N, N), -1, dtype=torch.int32)
+        pidx[lo, hi] = b
+        _pidx_cache[key] = (pidx, pidx.to(device).contiguous())
+        return _pidx_cache[key][1]
 
     def chunk_tab(self, chunk_rows):
         """Per-(seg,t) global chunk id from per-row chunk indices."""
