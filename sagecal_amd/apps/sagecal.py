@@ -119,6 +119,24 @@ def load_context(args):
     return ms, pack, clusters, device, dtype
 
 
+def _beam_geometry(pack, tile, cfg, tmjd):
+    """Source/pointing geometry of one tile, built once and kept on the
+    tile: the per-channel predicts of -B 4/5/6 and of the beamed residuals
+    all share it."""
+    from .. import beams
+    memo = getattr(tile, '_beam_geom', None)
+    from ..ops import dispatch
+    key = (dispatch.obj_token(pack), tuple(np.atleast_1d(tmjd).tolist()))
+    if memo is None or memo[0] != key:
+        ra, dec = beams._pack_radec(pack, tile.dec0)
+        memo = (key, beams.beam_geometry(cfg, ra, dec, tmjd))
+        try:
+            tile._beam_geom = memo
+        except AttributeError:
+            pass
+    return memo[1]
+
+
 def _predict_with_beam(ms, pack, tile, ti, args):
     """Coherencies with the station array beam applied (-B 1;
     predict_visibilities_multifreq_withbeam role). The MS must carry the
@@ -142,11 +160,13 @@ def _predict_with_beam(ms, pack, tile, ti, args):
     if et == 'auto':
         et = str(z['elem_type']) if 'elem_type' in z else 'synthetic'
     coeffs = None if et == 'synthetic' else et   # name -> LOFAR tables
+    geom = _beam_geometry(pack, tile, cfg, tmjd)
     if mode <= 3:
         return beams.predict_coh_withbeam(
             pack, tile.u, tile.v, tile.w, tile.freq0, tile.freq0,
             tile.fdelta, tile.tdelta, tile.dec0, cfg, tmjd,
-            ms.bb_tensor(), ms.Nbase, T, mode=mode, coeffs=coeffs)
+            ms.bb_tensor(), ms.Nbase, T, mode=mode, coeffs=coeffs,
+            geom=geom)
     # -B 4/5/6: per-channel beam (DOBEAM_*_WB): evaluate the beam at each
     # channel frequency and average, like the discrete channel model
     mode -= 3
@@ -156,7 +176,8 @@ def _predict_with_beam(ms, pack, tile, ti, args):
         c = beams.predict_coh_withbeam(
             pack, tile.u, tile.v, tile.w, float(f), tile.freq0,
             fdelta_ch, tile.tdelta, tile.dec0, cfg, tmjd,
-            ms.bb_tensor(), ms.Nbase, T, mode=mode, coeffs=coeffs)
+            ms.bb_tensor(), ms.Nbase, T, mode=mode, coeffs=coeffs,
+            geom=geom)
         acc = c if acc is None else acc + c
     return acc / len(tile.freqs)
 
@@ -184,7 +205,8 @@ def _predict_channel_with_beam(ms, pack, tile, ti, args, freq,
     return beams.predict_coh_withbeam(
         pack, tile.u, tile.v, tile.w, freq, tile.freq0, fdelta_ch,
         tile.tdelta, tile.dec0, cfg, tmjd, ms.bb_tensor(), ms.Nbase, T,
-        mode=mode, coeffs=coeffs)
+        mode=mode, coeffs=coeffs,
+        geom=_beam_geometry(pack, tile, cfg, tmjd))
 
 
 def uv_flags(tile, args):

@@ -55,6 +55,38 @@ def _direction_enu(ra, dec, lon, lat, gmst):
                     axis=-1), az, el
 
 
+class BeamGeometry:
+    """Host geometry of K sources over T timeslots as seen from the array
+    origin, shared by the array factor and the element pattern:
+      du    [T, K, 3] float64  ENU unit vector of the source minus that of
+                               the beam pointing
+      below [T, K]    bool     source under the horizon (el < 0)
+      az,el [T, K]    float64  source azimuth and elevation (rad)"""
+
+    def __init__(self, du, below, az, el):
+        self.du, self.below, self.az, self.el = du, below, az, el
+        self.T, self.K = below.shape
+
+
+def beam_geometry(cfg, ra, dec, tmjd):
+    """BeamGeometry of sources (ra, dec) at times tmjd (MJD days) for the
+    array of `cfg`: the per-timeslot numpy work of array_beam and of the
+    element pattern, done once."""
+    ra = np.atleast_1d(ra)
+    gmst = coords.jd_to_gmst(np.asarray(np.atleast_1d(tmjd)) + 2400000.5)
+    dus, azs, els = [], [], []
+    for g in np.atleast_1d(gmst):
+        usrc, az, el = _direction_enu(ra, dec, cfg.lon, cfg.lat, g)
+        upnt, _, _ = _direction_enu(cfg.b_ra0, cfg.b_dec0, cfg.lon,
+                                    cfg.lat, g)
+        dus.append(usrc - upnt)                        # [K, 3]
+        azs.append(az)
+        els.append(el)
+    el = np.stack(els)
+    return BeamGeometry(np.stack(dus).astype(np.float64), el < 0,
+                        np.stack(azs), el)
+
+
 def array_beam(cfg, ra, dec, freqs, tmjd, station_ids=None, device='cpu'):
     """Scalar array factor a[s, k, t, f] for stations s, sources k, times
     tmjd (days), freqs.
@@ -62,29 +94,28 @@ def array_beam(cfg, ra, dec, freqs, tmjd, station_ids=None, device='cpu'):
     arraybeam (stationbeam.c:49): af = (1/K) sum_elem exp(j 2 pi f/c
     r_e . (u_src - u_point)) — delay steering toward the beam pointing.
     """
-    ra = np.atleast_1d(ra)
-    tmjd = np.atleast_1d(tmjd)
-    freqs = np.atleast_1d(freqs)
-    gmst = coords.jd_to_gmst(np.asarray(tmjd) + 2400000.5)
+    return _array_factor(cfg, beam_geometry(cfg, ra, dec, tmjd), freqs,
+                         station_ids, device)
+
+
+def _station_elements(cfg, station_ids=None):
     nsta = len(cfg.element_enu) if isinstance(cfg.element_enu,
                                               (list, tuple)) else 1
     if station_ids is None:
         station_ids = list(range(nsta))
-    station_ids = list(station_ids)
-    elem_list = [cfg.elements(s) for s in station_ids]
+    return [cfg.elements(s) for s in list(station_ids)]
+
+
+def _array_factor(cfg, geom, freqs, station_ids=None, device='cpu'):
+    """array_beam on a ready BeamGeometry: [S, K, T, F] complex128."""
+    freqs = np.atleast_1d(freqs)
+    elem_list = _station_elements(cfg, station_ids)
     counts = {np.asarray(e).shape[0] for e in elem_list}
     fq = torch.as_tensor(freqs, dtype=torch.float64, device=device)
     # per-time geometry (shared across stations: one array origin)
-    dus, belows = [], []
-    for g in np.atleast_1d(gmst):
-        usrc, az, el = _direction_enu(ra, dec, cfg.lon, cfg.lat, g)
-        upnt, _, _ = _direction_enu(cfg.b_ra0, cfg.b_dec0, cfg.lon,
-                                    cfg.lat, g)
-        dus.append(torch.as_tensor(usrc - upnt, dtype=torch.float64,
-                                   device=device))     # [K, 3]
-        belows.append(torch.as_tensor(el < 0, device=device))
-    du = torch.stack(dus)                              # [T, K, 3]
-    below = torch.stack(belows)                        # [T, K]
+    du = torch.as_tensor(geom.du, dtype=torch.float64,
+                         device=device)                # [T, K, 3]
+    below = torch.as_tensor(geom.below, device=device)  # [T, K]
     if len(counts) == 1:
         # equal element counts: ONE batched pass — phases
         # [S,T,E,K] = elems[S,E,3] . du[T,K,3], then exp+mean over E and
@@ -348,12 +379,60 @@ def make_synthetic_element_coeffs(n0=4, freqs=(150e6,), seed=0,
                          mk(1))
 
 
+def array_beam_gains(cfg, geom, freq, device='cpu'):
+    """Real array-factor gains |af| [T, K, N] at one frequency, the `beam`
+    buffer of the predict kernels (beamgain, stationbeam.c:318). On a CUDA
+    device they come from k_array_beam (float32); on the CPU from the fp64
+    torch array factor, array_beam(...)[..., 0].abs() permuted (float64).
+    A one-element station has gain exactly 1 above the horizon."""
+    elem_list = [np.asarray(e, dtype=np.float64).reshape(-1, 3)
+                 for e in _station_elements(cfg)]
+    nelem = np.array([e.shape[0] for e in elem_list])
+    if torch.device(device).type == 'cuda':
+        from .ops import hip_host
+        if (nelem < 1).any():
+            raise ValueError("every station needs at least one element")
+        elem = np.zeros((len(elem_list), int(nelem.max()), 3))
+        for n, e in enumerate(elem_list):
+            elem[n, :e.shape[0]] = e
+        return hip_host.array_beam_gains(
+            torch.as_tensor(elem).to(device), nelem, geom.du, geom.below,
+            freq)
+    af = _array_factor(cfg, geom, [freq], None, device)  # [S, K, T, 1]
+    g = af[..., 0].abs().permute(2, 1, 0).contiguous()   # [T, K, S]
+    one = torch.as_tensor(nelem == 1, device=g.device)
+    up = ~torch.as_tensor(geom.below, device=g.device)
+    g[up[:, :, None] & one[None, None, :]] = 1.0
+    return g
+
+
+def _resolve_coeffs(coeffs, freq):
+    if coeffs is None:
+        return make_synthetic_element_coeffs(freqs=(freq,))
+    if isinstance(coeffs, str):
+        return LofarElementCoeffs.load(coeffs)
+    return coeffs
+
+
+def element_jones(coeffs, geom, freq):
+    """Dipole E-Jones of every (timeslot, source) of `geom`:
+    [T, K, 2, 2] complex128, one element_beam evaluation over all T*K
+    directions, zero below the horizon (kernel_element_beam role; one
+    pattern per array origin)."""
+    el = geom.el.reshape(-1)
+    E = element_beam(coeffs, geom.az.reshape(-1), np.maximum(el, 0.0),
+                     freq)
+    E[torch.from_numpy(el < 0)] = 0
+    return E.reshape(geom.T, geom.K, 2, 2)
+
+
 # ---------------------------------------------------------------------------
 # Beam-aware predict (CPU/torch; predict_withbeam.c analog)
 # ---------------------------------------------------------------------------
 
 def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
-                         cfg, tmjd, bb, Nbase, T, mode=1, coeffs=None):
+                         cfg, tmjd, bb, Nbase, T, mode=1, coeffs=None,
+                         geom=None):
     """Coherencies with the station beam applied per source/station
     (precalculate_coherencies_withbeam semantics, Dirac_radio.h:471):
     C'_pq(src) = g_p(src) C g_q(src)^* for the scalar array factor
@@ -365,9 +444,16 @@ def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
     reference (beamgain = |sum phasors|/K, stationbeam.c:318 and the GPU
     beam buffer predict_model.cu:843-852), not as a complex gain.
 
-    On GPU with mode 1 the whole predict runs as ONE fused kernel call:
-    the torch-computed gains feed k_predict_coh's beam argument
-    (kernel_array_beam -> kernel_coherencies structure).
+    On a GPU tensor every mode is ONE hip_host.predict_coh call
+    (kernel_array_beam / kernel_element_beam -> kernel_coherencies
+    structure): the gains of modes 1 and 2 come from k_array_beam, the
+    host-evaluated element E-Jones of modes 2 and 3 is applied per source
+    inside the predict kernels. On the CPU the per-source torch loop
+    below is the fp64 yardstick for that path.
+
+    `geom`: the BeamGeometry of (pack, cfg, tmjd) when the caller already
+    has it (per-channel loops build it once per tile); it does not change
+    the result.
     """
     from .ops import reference as R
     B = u.shape[0]
@@ -375,39 +461,35 @@ def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
     # per-source single predicts (phase/smear only), then scale by beam
     cdtype = torch.complex128 if u.dtype == torch.float64 \
         else torch.complex64
-    ra, dec = _pack_radec(pack, dec0)
     t_idx = torch.arange(B) // Nbase
     p = bb[:, 0]
     q = bb[:, 1]
     use_array = mode in (1, 2)
     use_elem = mode in (2, 3)
-    if use_array:
-        af = array_beam(cfg, ra, dec, [freq], tmjd)  # [S, K, T, 1]
-        af = af[..., 0].abs()                        # [S, K, T] real
-    if mode == 1 and u.is_cuda:
-        # fused kernel path (-B 1): beam [T, K, N] + pairs into
-        # k_predict_coh; falls back to the torch loop if the extension
-        # is unavailable (dispatch raises on GPU by policy)
+    if geom is None:
+        geom = beam_geometry(cfg, *_pack_radec(pack, dec0), tmjd)
+    if use_elem:
+        coeffs = _resolve_coeffs(coeffs, freq)
+    if u.is_cuda and (use_array or use_elem):
+        # device path: no per-source loop; a missing extension raises
         from .ops import hip_host
-        beam_t = af.permute(2, 1, 0).to(device=u.device,
-                                        dtype=torch.float32).contiguous()
+        beam_t = array_beam_gains(cfg, geom, freq, u.device) \
+            if use_array else None
+        ej = element_jones(coeffs, geom, freq).to(torch.complex64) \
+            .unsqueeze(2).to(u.device) if use_elem else None
         return hip_host.predict_coh(
             pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
-            beam=beam_t, pairs=bb[:Nbase].to(torch.int32),
-            Nbase=Nbase).to(cdtype)
+            beam=beam_t, pairs=bb, Nbase=Nbase, ejones=ej).to(cdtype)
+    if use_array:
+        af = _array_factor(cfg, geom, [freq])        # [S, K, T, 1]
+        af = af[..., 0].abs()                        # [S, K, T] real
     out = torch.zeros(M, B, 2, 2, dtype=cdtype, device=u.device)
     if use_elem:
         # element E-Jones per (source, time): one dipole pattern per
         # array origin (kernel_element_beam; DOBEAM_ELEMENT/FULL modes)
-        if coeffs is None:
-            coeffs = make_synthetic_element_coeffs(freqs=(freq,))
-        elif isinstance(coeffs, str):
-            coeffs = LofarElementCoeffs.load(coeffs)
-        gmst = coords.jd_to_gmst(np.asarray(np.atleast_1d(tmjd))
-                                 + 2400000.5)
         Es = []
-        for g in np.atleast_1d(gmst):
-            _, az, el = _direction_enu(ra, dec, cfg.lon, cfg.lat, g)
+        for t in range(geom.T):
+            az, el = geom.az[t], geom.el[t]
             E = element_beam(coeffs, az, np.maximum(el, 0.0), freq)
             E[torch.from_numpy(el < 0)] = 0
             Es.append(E)

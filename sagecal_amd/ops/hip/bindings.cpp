@@ -10,15 +10,17 @@ hipError_t launch_predict_coh(const double*, const double*, const double*,
     const float*, const float*, const float*, const float*, const float*,
     const float*, const float*, const float*, const float*, const float*,
     const float*, const int*, const int*, int, int, double, double,
-    double, const float*, const int*, int, int, int, float2*,
-    hipStream_t);
+    double, const float*, const int*, int, int, int, const float2*, int,
+    float2*, hipStream_t);
+hipError_t launch_array_beam(const double*, const int*, const double*,
+    const unsigned char*, int, int, int, double, float*, hipStream_t);
 hipError_t launch_shapelet_coh(const double*, const double*, const double*,
     int, int, const int*, const int*, const int*, const float*, const int*,
     const float*, const float*, const float*, const float*, const float*,
     const float*, const float*, const float*, const float*, const float*,
     const double*, const double*, const double*, const float*, int,
     const float*, const float*, double, double, double, const float*,
-    const int*, int, int, int, float2*, hipStream_t);
+    const int*, int, int, int, const float2*, int, float2*, hipStream_t);
 hipError_t launch_jtj_accum(const float2*, const float2*, const float2*,
     const int*, const int*, const int*, const float*, int, int, int, int,
     int, float2*, float2*, float*, int*, float2*, float2*, float2*, float*,
@@ -51,6 +53,42 @@ static const float2* ccptr(const torch::Tensor& t) {
   return reinterpret_cast<const float2*>(t.data_ptr());
 }
 
+// Checks an optional E-Jones buffer [T, K, NE, 2, 2] complex64 against the
+// rows and the beam; returns its pointer (null without one) and sets NE,
+// Ktot and Nsta. The kernels read pairs on every row with it.
+static const float2* ejones_arg(
+    const c10::optional<torch::Tensor>& ejones,
+    const c10::optional<torch::Tensor>& beam,
+    const c10::optional<torch::Tensor>& pairs, const torch::Tensor& u,
+    int64_t Nbase, int64_t Nsta_in, int& NE, int& Ktot, int& Nsta) {
+  NE = 0;
+  if (!ejones.has_value()) return nullptr;
+  const torch::Tensor& e = *ejones;
+  const int64_t R = u.size(0);
+  TORCH_CHECK(e.is_cuda() && e.device() == u.device() &&
+              e.scalar_type() == torch::kComplexFloat && e.is_contiguous() &&
+              e.dim() == 5 && e.size(3) == 2 && e.size(4) == 2,
+              "ejones must be contiguous [T, K, NE, 2, 2] complex64");
+  TORCH_CHECK(pairs.has_value() && Nbase > 0,
+              "ejones needs the station-pair table and Nbase");
+  TORCH_CHECK(pairs->device() == u.device() &&
+              pairs->scalar_type() == torch::kInt && pairs->is_contiguous() &&
+              pairs->numel() == 2 * Nbase,
+              "pairs must be contiguous [Nbase, 2] int32");
+  TORCH_CHECK(e.size(0) * Nbase == R, "ejones timeslots * Nbase != rows");
+  TORCH_CHECK(Nsta_in > 0, "ejones needs the station count Nsta");
+  TORCH_CHECK(e.size(2) == 1 || e.size(2) == Nsta_in,
+              "ejones must hold 1 or Nsta patterns per source");
+  if (beam.has_value())
+    TORCH_CHECK(beam->size(0) == e.size(0) && beam->size(1) == e.size(1) &&
+                beam->size(2) == Nsta_in,
+                "beam and ejones disagree on [T, K] or Nsta");
+  NE = (int)e.size(2);
+  Ktot = (int)e.size(1);
+  Nsta = (int)Nsta_in;
+  return reinterpret_cast<const float2*>(e.data_ptr());
+}
+
 torch::Tensor predict_coh(
     torch::Tensor u, torch::Tensor v, torch::Tensor w,
     torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
@@ -60,7 +98,7 @@ torch::Tensor predict_coh(
     torch::Tensor sphi, torch::Tensor r1, torch::Tensor stype,
     torch::Tensor cluster_off, double freq, double fdelta2, double tdelta,
     c10::optional<torch::Tensor> beam, c10::optional<torch::Tensor> pairs,
-    int64_t Nbase) {
+    int64_t Nbase, c10::optional<torch::Tensor> ejones, int64_t Nsta_ej) {
   const int R = u.size(0);
   const int M = cluster_off.size(0) - 1;
   auto out = torch::empty({M, R, 4},
@@ -77,6 +115,10 @@ torch::Tensor predict_coh(
     Ktot = beam->size(1);
     Nsta = beam->size(2);
   }
+  int NE = 0;
+  const float2* ej_p = ejones_arg(ejones, beam, pairs, u, Nbase, Nsta_ej,
+                                  NE, Ktot, Nsta);
+  if (ej_p != nullptr) pairs_p = pairs->data_ptr<int>();
   CHECK_HIP(launch_predict_coh(
       u.data_ptr<double>(), v.data_ptr<double>(), w.data_ptr<double>(),
       ll.data_ptr<double>(), mm.data_ptr<double>(), nn1.data_ptr<double>(),
@@ -85,7 +127,7 @@ torch::Tensor predict_coh(
       eP.data_ptr<float>(), cxi.data_ptr<float>(), sxi.data_ptr<float>(),
       cphi.data_ptr<float>(), sphi.data_ptr<float>(), r1.data_ptr<float>(),
       stype.data_ptr<int>(), cluster_off.data_ptr<int>(), M, R, freq,
-      fdelta2, tdelta, beam_p, pairs_p, (int)Nbase, Ktot, Nsta,
+      fdelta2, tdelta, beam_p, pairs_p, (int)Nbase, Ktot, Nsta, ej_p, NE,
       cptr(out), cur_stream()));
   return out;
 }
@@ -103,7 +145,7 @@ void shapelet_coh_add(
     torch::Tensor rec, torch::Tensor flux, torch::Tensor r1,
     double freq, double fdelta2, double tdelta,
     c10::optional<torch::Tensor> beam, c10::optional<torch::Tensor> pairs,
-    int64_t Nbase) {
+    int64_t Nbase, c10::optional<torch::Tensor> ejones, int64_t Nsta_ej) {
   const int64_t R = u.size(0);
   const int64_t S = src.size(0);
   auto chk = [&](const torch::Tensor& t, torch::ScalarType ty, int64_t n,
@@ -159,6 +201,10 @@ void shapelet_coh_add(
     Ktot = beam->size(1);
     Nsta = beam->size(2);
   }
+  int NE = 0;
+  const float2* ej_p = ejones_arg(ejones, beam, pairs, u, Nbase, Nsta_ej,
+                                  NE, Ktot, Nsta);
+  if (ej_p != nullptr) pairs_p = pairs->data_ptr<int>();
   CHECK_HIP(launch_shapelet_coh(
       u.data_ptr<double>(), v.data_ptr<double>(), w.data_ptr<double>(),
       (int)R, (int)S, src.data_ptr<int>(), cluster.data_ptr<int>(),
@@ -169,8 +215,39 @@ void shapelet_coh_add(
       ceP.data_ptr<float>(), seP.data_ptr<float>(), ll.data_ptr<double>(),
       mm.data_ptr<double>(), nn1.data_ptr<double>(), rec.data_ptr<float>(),
       (int)rec.size(1), flux.data_ptr<float>(), r1.data_ptr<float>(), freq,
-      fdelta2, tdelta, beam_p, pairs_p, (int)Nbase, Ktot, Nsta, cptr(out),
-      cur_stream()));
+      fdelta2, tdelta, beam_p, pairs_p, (int)Nbase, Ktot, Nsta, ej_p, NE,
+      cptr(out), cur_stream()));
+}
+
+// gain[t,k,n] of k_array_beam: elem [N, Emax, 3] float64, nelem [N] int32
+// (the caller has checked 1 <= nelem <= Emax on the host), du [T, K, 3]
+// float64, below [T, K] uint8, kf = 2 pi f / c. Returns [T, K, N] float32.
+torch::Tensor array_beam_gains(
+    torch::Tensor elem, torch::Tensor nelem, torch::Tensor du,
+    torch::Tensor below, double kf) {
+  TORCH_CHECK(elem.is_cuda() && elem.scalar_type() == torch::kDouble &&
+              elem.is_contiguous() && elem.dim() == 3 && elem.size(2) == 3 &&
+              elem.size(1) > 0, "elem must be contiguous [N, Emax, 3] float64");
+  const int64_t N = elem.size(0), Emax = elem.size(1);
+  TORCH_CHECK(nelem.device() == elem.device() &&
+              nelem.scalar_type() == torch::kInt && nelem.is_contiguous() &&
+              nelem.numel() == N, "nelem must be contiguous [N] int32");
+  TORCH_CHECK(du.device() == elem.device() &&
+              du.scalar_type() == torch::kDouble && du.is_contiguous() &&
+              du.dim() == 3 && du.size(2) == 3,
+              "du must be contiguous [T, K, 3] float64");
+  const int64_t T = du.size(0), K = du.size(1);
+  TORCH_CHECK(below.device() == elem.device() &&
+              below.scalar_type() == torch::kByte && below.is_contiguous() &&
+              below.dim() == 2 && below.size(0) == T && below.size(1) == K,
+              "below must be contiguous [T, K] uint8");
+  TORCH_CHECK(T * K < (int64_t(1) << 31), "too many (timeslot, source) pairs");
+  auto gain = torch::empty({T, K, N},
+      torch::dtype(torch::kFloat).device(elem.device()));
+  CHECK_HIP(launch_array_beam(elem.data_ptr<double>(), nelem.data_ptr<int>(),
+      du.data_ptr<double>(), below.data_ptr<uint8_t>(), (int)N, (int)Emax,
+      (int)(T * K), kf, gain.data_ptr<float>(), cur_stream()));
+  return gain;
 }
 
 std::vector<torch::Tensor> jtj_jtr(
@@ -319,7 +396,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sphi"), py::arg("r1"), py::arg("stype"),
         py::arg("cluster_off"), py::arg("freq"), py::arg("fdelta2"),
         py::arg("tdelta"), py::arg("beam") = py::none(),
-        py::arg("pairs") = py::none(), py::arg("Nbase") = 0);
+        py::arg("pairs") = py::none(), py::arg("Nbase") = 0,
+        py::arg("ejones") = py::none(), py::arg("Nsta") = 0);
   m.def("shapelet_coh_add", &shapelet_coh_add,
         "add shapelet-source coherencies into out (gfx950)",
         py::arg("out"), py::arg("u"), py::arg("v"), py::arg("w"),
@@ -330,7 +408,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("mm"), py::arg("nn1"), py::arg("rec"), py::arg("flux"),
         py::arg("r1"), py::arg("freq"), py::arg("fdelta2"),
         py::arg("tdelta"), py::arg("beam") = py::none(),
-        py::arg("pairs") = py::none(), py::arg("Nbase") = 0);
+        py::arg("pairs") = py::none(), py::arg("Nbase") = 0,
+        py::arg("ejones") = py::none(), py::arg("Nsta") = 0);
+  m.def("array_beam_gains", &array_beam_gains,
+        "station array-factor gains [T, K, N] (gfx950)", py::arg("elem"),
+        py::arg("nelem"), py::arg("du"), py::arg("below"), py::arg("kf"));
   m.def("jtj_jtr", &jtj_jtr, "fused JtJ/Jtr assembly (gfx950)");
   m.def("model_cost", &model_cost, "per-chunk model cost (gfx950)");
   m.def("apply_jones", &apply_jones, "model apply / residual (gfx950)");

@@ -15,9 +15,20 @@ hipError_t launch_predict_coh(
     const float* sphi, const float* r1, const int* stype,
     const int* cluster_off, int M, int R, double freq, double fdelta2,
     double tdelta, const float* beam, const int* pairs, int Nbase,
-    int Ktot, int Nsta, float2* out, hipStream_t stream) {
+    int Ktot, int Nsta, const float2* ejones, int NE, float2* out,
+    hipStream_t stream) {
   const int tb = 128;
   const int nb = (R + tb - 1) / tb;
+  if (ejones != nullptr) {
+    // E-Jones variant; it reads pairs on every row
+    if (pairs == nullptr || Nbase <= 0 || (NE != 1 && NE != Nsta))
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_predict_coh_ej, dim3(nb), dim3(tb), 0, stream,
+        u, v, w, ll, mm, nn1, sI, sQ, sU, sV, eX, eY, eP, cxi, sxi, cphi,
+        sphi, r1, stype, cluster_off, M, R, freq, fdelta2, tdelta,
+        beam, pairs, Nbase, Ktot, Nsta, ejones, NE, out);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_predict_coh, dim3(nb), dim3(tb), 0, stream,
       u, v, w, ll, mm, nn1, sI, sQ, sU, sV, eX, eY, eP, cxi, sxi, cphi,
       sphi, r1, stype, cluster_off, M, R, freq, fdelta2, tdelta,
@@ -34,15 +45,38 @@ hipError_t launch_shapelet_coh(
     const double* ll, const double* mm, const double* nn1,
     const float* rec, int nmax, const float* flux, const float* r1,
     double freq, double fdelta2, double tdelta, const float* beam,
-    const int* pairs, int Nbase, int Ktot, int Nsta, float2* out,
-    hipStream_t stream) {
+    const int* pairs, int Nbase, int Ktot, int Nsta, const float2* ejones,
+    int NE, float2* out, hipStream_t stream) {
   if (S <= 0 || R <= 0) return hipSuccess;
   const int tb = 128;
   const int nb = (R + tb - 1) / tb;
+  if (ejones != nullptr) {
+    if (pairs == nullptr || Nbase <= 0 || (NE != 1 && NE != Nsta))
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_shapelet_coh_ej, dim3(nb), dim3(tb), 0, stream,
+        u, v, w, R, S, src, cluster, n0, beta, off, coef, cxi, sxi, cphi,
+        sphi, psign, a, b, ceP, seP, ll, mm, nn1, rec, nmax, flux, r1,
+        freq, fdelta2, tdelta, beam, pairs, Nbase, Ktot, Nsta, ejones, NE,
+        out);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_shapelet_coh, dim3(nb), dim3(tb), 0, stream,
       u, v, w, R, S, src, cluster, n0, beta, off, coef, cxi, sxi, cphi,
       sphi, psign, a, b, ceP, seP, ll, mm, nn1, rec, nmax, flux, r1,
       freq, fdelta2, tdelta, beam, pairs, Nbase, Ktot, Nsta, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_array_beam(
+    const double* elem, const int* nelem, const double* du,
+    const unsigned char* below, int N, int Emax, int TK, double kf,
+    float* gain, hipStream_t stream) {
+  if (N <= 0 || TK <= 0) return hipSuccess;
+  if (Emax <= 0) return hipErrorInvalidValue;
+  const int tb = 256;
+  hipLaunchKernelGGL(k_array_beam,
+      dim3((TK + tb - 1) / tb, (N + AB_NSTA - 1) / AB_NSTA), dim3(tb), 0,
+      stream, elem, nelem, du, below, N, Emax, TK, kf, gain);
   return hipGetLastError();
 }
 

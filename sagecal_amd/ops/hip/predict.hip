@@ -17,6 +17,15 @@
 // (timeslot, source, station) [T, K, N] (beamgain = |sum phasors|/K,
 // stationbeam.c:318 — the reference's array factor is real), and each
 // source's contribution is scaled by beam[t,g,sta1]*beam[t,g,sta2].
+//
+// Optional element-beam path (-B 2/3, DOBEAM_FULL / DOBEAM_ELEMENT,
+// predict_model.cu:843-852 with elementgain): the _ej kernels take the
+// dipole E-Jones per (timeslot, source, pattern) [T, K, NE, 2, 2]
+// complex64, NE = 1 (one pattern per array origin) or Nsta, and add
+// g_p g_q E_p C E_q^H per source. The sandwich differs per source, so the
+// accumulators are the four coherency entries instead of four Stokes sums.
+// They are compile-time variants (template parameter EJ) of one body: the
+// kernels without E-Jones carry none of this code and no branch for it.
 #include "common.h"
 
 #define SRC_TILE 64
@@ -30,6 +39,14 @@ struct SrcTile {
   int   stype[SRC_TILE];
 };
 
+// cos/sin of an fp64 phase: argument reduced in fp64, then the fast float
+// sincos. Shared by phase_smear and k_array_beam.
+__device__ __forceinline__ void sincos_reduced(double ph, float* sp,
+                                               float* cp) {
+  const float phr = (float)fmod(ph, 6.283185307179586476925286766559);
+  __sincosf(phr, sp, cp);
+}
+
 // Smeared phase term of one source at one row, shared by k_predict_coh and
 // k_shapelet_coh: exp(i*phase) * freq smearing * time smearing.
 __device__ __forceinline__ cf phase_smear(double ur, double vr, double wr,
@@ -41,9 +58,8 @@ __device__ __forceinline__ cf phase_smear(double ur, double vr, double wr,
       (ur * l + vr * m + wr * n1);
   // phase at this channel, arg-reduced in fp64 then fast float sincos
   const double ph = fma(G, freq, 0.0);
-  const float phr = (float)fmod(ph, 6.283185307179586476925286766559);
   float sp, cp;
-  __sincosf(phr, &sp, &cp);
+  sincos_reduced(ph, &sp, &cp);
   // freq smearing |sinc(G*fdelta/2)| (predict.c:178-189)
   float sm = 1.0f;
   const float smf = (float)(G * fdelta2);
@@ -54,37 +70,66 @@ __device__ __forceinline__ cf phase_smear(double ur, double vr, double wr,
   return {cp * sm, sp * sm};
 }
 
-extern "C" __global__ void __launch_bounds__(128)
-k_predict_coh(const double* __restrict__ u, const double* __restrict__ v,
-              const double* __restrict__ w,
-              const double* __restrict__ ll, const double* __restrict__ mm,
-              const double* __restrict__ nn1,
-              const float* __restrict__ sI, const float* __restrict__ sQ,
-              const float* __restrict__ sU, const float* __restrict__ sV,
-              const float* __restrict__ eX, const float* __restrict__ eY,
-              const float* __restrict__ eP, const float* __restrict__ cxi,
-              const float* __restrict__ sxi, const float* __restrict__ cphi,
-              const float* __restrict__ sphi, const float* __restrict__ r1t,
-              const int* __restrict__ stype,
-              const int* __restrict__ cluster_off, int M, int R,
-              double freq, double fdelta2,      // channel halfwidth [Hz]
-              double tdelta,
-              const float* __restrict__ beam,   // [T, K, N] or null
-              const int* __restrict__ pairs,    // [Nbase, 2] (with beam)
-              int Nbase, int Ktot, int Nsta,
-              float2* __restrict__ out) {
+// acc += g * E_p * (phc * [[I+Q, U+iV],[U-iV, I-Q]]) * E_q^H, the
+// contribution of one source to the four coherency entries of one row.
+// ep, eq: row-major 2x2 complex.
+__device__ __forceinline__ void ej_accumulate(cf phc, float fI, float fQ,
+                                              float fU, float fV, float g,
+                                              const cf* ep, const cf* eq,
+                                              cf* acc) {
+  const cf E[4] = {ep[0], ep[1], ep[2], ep[3]};
+  const cf F[4] = {eq[0], eq[1], eq[2], eq[3]};
+  phc = cscale(phc, g);
+  const cf C[4] = {cscale(phc, fI + fQ), cmul(phc, {fU, fV}),
+                   cmul(phc, {fU, -fV}), cscale(phc, fI - fQ)};
+  cf EC[4], S[4];
+  m2mul(E, C, EC);
+  m2mulh(EC, F, S);
+  for (int i = 0; i < 4; ++i) acc[i] = cadd(acc[i], S[i]);
+}
+
+#define PREDICT_COH_PARAMS                                                  \
+    const double* __restrict__ u, const double* __restrict__ v,             \
+    const double* __restrict__ w, const double* __restrict__ ll,            \
+    const double* __restrict__ mm, const double* __restrict__ nn1,          \
+    const float* __restrict__ sI, const float* __restrict__ sQ,             \
+    const float* __restrict__ sU, const float* __restrict__ sV,             \
+    const float* __restrict__ eX, const float* __restrict__ eY,             \
+    const float* __restrict__ eP, const float* __restrict__ cxi,            \
+    const float* __restrict__ sxi, const float* __restrict__ cphi,          \
+    const float* __restrict__ sphi, const float* __restrict__ r1t,          \
+    const int* __restrict__ stype, const int* __restrict__ cluster_off,     \
+    int M, int R, double freq,                                              \
+    double fdelta2,                   /* channel halfwidth [Hz] */          \
+    double tdelta,                                                          \
+    const float* __restrict__ beam,   /* [T, K, N] or null */               \
+    const int* __restrict__ pairs,    /* [Nbase, 2] (with beam or EJ) */    \
+    int Nbase, int Ktot, int Nsta
+#define PREDICT_COH_ARGS                                                    \
+    u, v, w, ll, mm, nn1, sI, sQ, sU, sV, eX, eY, eP, cxi, sxi, cphi, sphi, \
+    r1t, stype, cluster_off, M, R, freq, fdelta2, tdelta, beam, pairs,      \
+    Nbase, Ktot, Nsta
+
+template <bool EJ>
+__device__ __forceinline__ void predict_coh_body(
+    PREDICT_COH_PARAMS,
+    const float2* __restrict__ ejones,  // [T, K, NE, 2, 2] (EJ)
+    int NE,
+    float2* __restrict__ out) {
   __shared__ SrcTile tile;
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = r < R;
-  // beam indexing state (only touched when beam != null)
+  // beam indexing state (only touched when beam != null, or with EJ)
   int b_sta1 = 0, b_sta2 = 0;
   size_t b_toff = 0;
-  if (beam != nullptr && live) {
+  if ((EJ || beam != nullptr) && live) {
     const int t = r / Nbase, bl = r - t * Nbase;
     b_sta1 = pairs[2 * bl];
     b_sta2 = pairs[2 * bl + 1];
     b_toff = (size_t)t * Ktot;
   }
+  // E-Jones pattern of each station: its own, or pattern 0 when NE == 1
+  const int e_sta1 = NE == 1 ? 0 : b_sta1, e_sta2 = NE == 1 ? 0 : b_sta2;
   double ur = 0, vr = 0, wr = 0;
   float blf = 0.f;
   if (live) {
@@ -99,6 +144,8 @@ k_predict_coh(const double* __restrict__ u, const double* __restrict__ v,
     const int s0 = cluster_off[ci], s1 = cluster_off[ci + 1];
     // accumulators: IIl/QQl/UUl/VVl sums as complex
     cf aI = {0.f, 0.f}, aQ = {0.f, 0.f}, aU = {0.f, 0.f}, aV = {0.f, 0.f};
+    // with EJ: the four coherency entries themselves
+    cf acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
     for (int base = s0; base < s1; base += SRC_TILE) {
       const int nt = min(SRC_TILE, s1 - base);
       __syncthreads();
@@ -144,6 +191,18 @@ k_predict_coh(const double* __restrict__ u, const double* __restrict__ v,
           }
           // st==4 (shapelet): fluxes are zero here, k_shapelet_coh adds them
         }
+        if constexpr (EJ) {
+          const size_t tk = b_toff + (size_t)(base + k);
+          float g = 1.0f;
+          if (beam != nullptr) {
+            const float* bg = beam + tk * (size_t)Nsta;
+            g = bg[b_sta1] * bg[b_sta2];
+          }
+          const cf* ej = ejones + tk * (size_t)NE * 4;
+          ej_accumulate(phc, tile.sI[k], tile.sQ[k], tile.sU[k], tile.sV[k],
+                        g, ej + 4 * e_sta1, ej + 4 * e_sta2, acc);
+          continue;
+        }
         if (beam != nullptr) {
           const float* bg = beam +
               (b_toff + (size_t)(base + k)) * (size_t)Nsta;
@@ -158,13 +217,29 @@ k_predict_coh(const double* __restrict__ u, const double* __restrict__ v,
     if (live) {
       // Stokes -> coherency [[I+Q, U+jV],[U-jV, I-Q]] (predict.c:228-235)
       float2* o = out + ((size_t)ci * R + r) * 4;
-      o[0] = cadd(aI, aQ);
-      o[1] = {aU.x - aV.y, aU.y + aV.x};
-      o[2] = {aU.x + aV.y, aU.y - aV.x};
-      o[3] = csub(aI, aQ);
+      if constexpr (EJ) {
+        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2]; o[3] = acc[3];
+      } else {
+        o[0] = cadd(aI, aQ);
+        o[1] = {aU.x - aV.y, aU.y + aV.x};
+        o[2] = {aU.x + aV.y, aU.y - aV.x};
+        o[3] = csub(aI, aQ);
+      }
     }
     __syncthreads();
   }
+}
+
+extern "C" __global__ void __launch_bounds__(128)
+k_predict_coh(PREDICT_COH_PARAMS, float2* __restrict__ out) {
+  predict_coh_body<false>(PREDICT_COH_ARGS, nullptr, 0, out);
+}
+
+// E-Jones variant: pairs, Nbase and Ktot are required; beam may be null.
+extern "C" __global__ void __launch_bounds__(128)
+k_predict_coh_ej(PREDICT_COH_PARAMS, const float2* __restrict__ ejones,
+                 int NE, float2* __restrict__ out) {
+  predict_coh_body<true>(PREDICT_COH_ARGS, ejones, NE, out);
 }
 
 // Shapelet sources, added into the coherencies k_predict_coh has written
@@ -185,37 +260,47 @@ k_predict_coh(const double* __restrict__ u, const double* __restrict__ v,
 // and 2 pi a b are folded into coef on the host. phi_n is the normalised
 // Hermite function, phi_0 = e^{-x^2/2}/sqrt(2), phi_n = x sqrt(2/n)
 // phi_{n-1} - sqrt((n-1)/n) phi_{n-2}; rec holds the two constants per n.
-extern "C" __global__ void __launch_bounds__(128)
-k_shapelet_coh(const double* __restrict__ u, const double* __restrict__ v,
-               const double* __restrict__ w, int R, int S,
-               const int* __restrict__ src, const int* __restrict__ cluster,
-               const int* __restrict__ n0t, const float* __restrict__ betat,
-               const int* __restrict__ off, const float* __restrict__ coef,
-               const float* __restrict__ cxi, const float* __restrict__ sxi,
-               const float* __restrict__ cphi, const float* __restrict__ sphi,
-               const float* __restrict__ psign, const float* __restrict__ at,
-               const float* __restrict__ bt, const float* __restrict__ ceP,
-               const float* __restrict__ seP,
-               const double* __restrict__ ll, const double* __restrict__ mm,
-               const double* __restrict__ nn1,
-               const float* __restrict__ rec, int nmax,  // [2, nmax]
-               const float* __restrict__ flux,           // [4, S] I,Q,U,V
-               const float* __restrict__ r1t,            // [S]
-               double freq, double fdelta2, double tdelta,
-               const float* __restrict__ beam,   // [T, K, N] or null
-               const int* __restrict__ pairs,    // [Nbase, 2] (with beam)
-               int Nbase, int Ktot, int Nsta,
-               float2* out) {                    // [M, R, 4], added into
+#define SHAPELET_COH_PARAMS                                                 \
+    const double* __restrict__ u, const double* __restrict__ v,             \
+    const double* __restrict__ w, int R, int S,                             \
+    const int* __restrict__ src, const int* __restrict__ cluster,           \
+    const int* __restrict__ n0t, const float* __restrict__ betat,           \
+    const int* __restrict__ off, const float* __restrict__ coef,            \
+    const float* __restrict__ cxi, const float* __restrict__ sxi,           \
+    const float* __restrict__ cphi, const float* __restrict__ sphi,         \
+    const float* __restrict__ psign, const float* __restrict__ at,          \
+    const float* __restrict__ bt, const float* __restrict__ ceP,            \
+    const float* __restrict__ seP, const double* __restrict__ ll,           \
+    const double* __restrict__ mm, const double* __restrict__ nn1,          \
+    const float* __restrict__ rec, int nmax,  /* [2, nmax] */               \
+    const float* __restrict__ flux,           /* [4, S] I,Q,U,V */          \
+    const float* __restrict__ r1t,            /* [S] */                     \
+    double freq, double fdelta2, double tdelta,                             \
+    const float* __restrict__ beam,   /* [T, K, N] or null */               \
+    const int* __restrict__ pairs,    /* [Nbase, 2] (with beam) */          \
+    int Nbase, int Ktot, int Nsta
+#define SHAPELET_COH_ARGS                                                   \
+    u, v, w, R, S, src, cluster, n0t, betat, off, coef, cxi, sxi, cphi,     \
+    sphi, psign, at, bt, ceP, seP, ll, mm, nn1, rec, nmax, flux, r1t, freq, \
+    fdelta2, tdelta, beam, pairs, Nbase, Ktot, Nsta
+
+template <bool EJ>
+__device__ __forceinline__ void shapelet_coh_body(
+    SHAPELET_COH_PARAMS,
+    const float2* __restrict__ ejones,  // [T, K, NE, 2, 2] (EJ)
+    int NE,
+    float2* out) {                      // [M, R, 4], added into
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
   int b_sta1 = 0, b_sta2 = 0;
   size_t b_toff = 0;
-  if (beam != nullptr) {
+  if (EJ || beam != nullptr) {
     const int t = r / Nbase, bl = r - t * Nbase;
     b_sta1 = pairs[2 * bl];
     b_sta2 = pairs[2 * bl + 1];
     b_toff = (size_t)t * Ktot;
   }
+  const int e_sta1 = NE == 1 ? 0 : b_sta1, e_sta2 = NE == 1 ? 0 : b_sta2;
   const double ur = u[r], vr = v[r], wr = w[r];
   const float blf = (float)(sqrt(ur * ur + vr * vr + wr * wr) * freq);
   const float uf = (float)(ur * freq), vf = (float)(vr * freq),
@@ -225,9 +310,15 @@ k_shapelet_coh(const double* __restrict__ u, const double* __restrict__ v,
   const float* rec1 = rec + nmax;   // sqrt((n-1)/n)
 
   cf aI = {0.f, 0.f}, aQ = {0.f, 0.f}, aU = {0.f, 0.f}, aV = {0.f, 0.f};
+  // with EJ: the four coherency entries themselves
+  cf acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
   auto flush = [&](int ci) {
-    // Stokes -> coherency [[I+Q, U+jV],[U-jV, I-Q]] (predict.c:228-235)
     float2* o = out + ((size_t)ci * R + r) * 4;
+    if constexpr (EJ) {
+      for (int i = 0; i < 4; ++i) o[i] = cadd(o[i], acc[i]);
+      return;
+    }
+    // Stokes -> coherency [[I+Q, U+jV],[U-jV, I-Q]] (predict.c:228-235)
     o[0] = cadd(o[0], cadd(aI, aQ));
     o[1] = cadd(o[1], {aU.x - aV.y, aU.y + aV.x});
     o[2] = cadd(o[2], {aU.x + aV.y, aU.y - aV.x});
@@ -239,6 +330,7 @@ k_shapelet_coh(const double* __restrict__ u, const double* __restrict__ v,
     if (ci != cur) {
       flush(cur);
       aI = {0.f, 0.f}; aQ = {0.f, 0.f}; aU = {0.f, 0.f}; aV = {0.f, 0.f};
+      for (int i = 0; i < 4; ++i) acc[i] = {0.f, 0.f};
       cur = ci;
     }
     cf phc = phase_smear(ur, vr, wr, ll[s], mm[s], nn1[s], freq, fdelta2,
@@ -281,6 +373,19 @@ k_shapelet_coh(const double* __restrict__ u, const double* __restrict__ v,
       else        { re += pv * se; im += pv * so; }
     }
     phc = cmul(phc, {re, im});
+    if constexpr (EJ) {
+      const size_t tk = b_toff + (size_t)src[s];
+      float g = 1.0f;
+      if (beam != nullptr) {
+        const float* bg = beam + tk * (size_t)Nsta;
+        g = bg[b_sta1] * bg[b_sta2];
+      }
+      const cf* ej = ejones + tk * (size_t)NE * 4;
+      ej_accumulate(phc, flux[s], flux[S + s], flux[2 * S + s],
+                    flux[3 * S + s], g, ej + 4 * e_sta1, ej + 4 * e_sta2,
+                    acc);
+      continue;
+    }
     if (beam != nullptr) {
       const float* bg = beam + (b_toff + (size_t)src[s]) * (size_t)Nsta;
       phc = cscale(phc, bg[b_sta1] * bg[b_sta2]);
@@ -291,4 +396,87 @@ k_shapelet_coh(const double* __restrict__ u, const double* __restrict__ v,
     aV = cadd(aV, cscale(phc, flux[3 * S + s]));
   }
   flush(cur);
+}
+
+extern "C" __global__ void __launch_bounds__(128)
+k_shapelet_coh(SHAPELET_COH_PARAMS, float2* out) {
+  shapelet_coh_body<false>(SHAPELET_COH_ARGS, nullptr, 0, out);
+}
+
+// E-Jones variant: E is indexed by the table's source index src[s], like
+// the beam; pairs, Nbase and Ktot are required, beam may be null.
+extern "C" __global__ void __launch_bounds__(128)
+k_shapelet_coh_ej(SHAPELET_COH_PARAMS, const float2* __restrict__ ejones,
+                  int NE, float2* out) {
+  shapelet_coh_body<true>(SHAPELET_COH_ARGS, ejones, NE, out);
+}
+
+// Array-factor gains of every station toward every (timeslot, source), the
+// beam buffer of the predict kernels (kernel_array_beam role,
+// predict_model.cu:129; arraybeam, stationbeam.c:49):
+//   gain[t,k,n] = below[t,k] ? 0
+//               : |(1/nelem[n]) sum_e exp(i kf elem[n,e] . du[t,k])|
+// with kf = 2 pi f / c. One thread per (t,k); the block walks AB_NSTA
+// consecutive stations, staging each station's elements through LDS in
+// tiles of AB_ETILE (any Emax), and every thread sums a station's phasors
+// in element order — a fixed order, so results repeat bit for bit. The
+// output is strided by N along (t,k); walking AB_NSTA stations per block
+// lets each thread write AB_NSTA adjacent floats instead of one, and the
+// stores stay 1/nelem of the sincos work. A one-element station has gain 1
+// by definition; its rounded cos^2 + sin^2 is not used.
+#define AB_ETILE 128
+#define AB_NSTA 4
+
+extern "C" __global__ void __launch_bounds__(256)
+k_array_beam(const double* __restrict__ elem,   // [N, Emax, 3] ENU, padded
+             const int* __restrict__ nelem,     // [N], 1 <= nelem <= Emax
+             const double* __restrict__ du,     // [TK, 3]
+             const unsigned char* __restrict__ below,  // [TK]
+             int N, int Emax, int TK, double kf,
+             float* __restrict__ gain) {        // [TK, N]
+  __shared__ double ex[AB_ETILE], ey[AB_ETILE], ez[AB_ETILE];
+  const int tk = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = tk < TK;
+  double dx = 0, dy = 0, dz = 0;
+  bool dark = true;
+  if (live) {
+    dx = kf * du[3 * (size_t)tk];
+    dy = kf * du[3 * (size_t)tk + 1];
+    dz = kf * du[3 * (size_t)tk + 2];
+    dark = below[tk] != 0;
+  }
+  const int n0 = blockIdx.y * AB_NSTA;
+  float g[AB_NSTA];
+#pragma unroll
+  for (int j = 0; j < AB_NSTA; ++j) {
+    g[j] = 0.f;
+    const int n = n0 + j;          // block-uniform
+    if (n < N) {
+      const int ne = nelem[n];
+      float re = 0.f, im = 0.f;
+      for (int e0 = 0; e0 < ne; e0 += AB_ETILE) {
+        const int nt = min(AB_ETILE, ne - e0);
+        __syncthreads();
+        for (int i = threadIdx.x; i < nt; i += blockDim.x) {
+          const double* p = elem + ((size_t)n * Emax + e0 + i) * 3;
+          ex[i] = p[0]; ey[i] = p[1]; ez[i] = p[2];
+        }
+        __syncthreads();
+        if (dark) continue;
+        for (int i = 0; i < nt; ++i) {
+          float s, c;
+          sincos_reduced(ex[i] * dx + ey[i] * dy + ez[i] * dz, &s, &c);
+          re += c;
+          im += s;
+        }
+      }
+      if (!dark)
+        g[j] = ne == 1 ? 1.0f : sqrtf(re * re + im * im) / (float)ne;
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < AB_NSTA; ++j)
+      if (n0 + j < N) gain[(size_t)tk * N + n0 + j] = g[j];
+  }
 }

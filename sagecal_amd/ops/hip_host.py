@@ -197,6 +197,7 @@ class GPUPack:
         f32 = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
         f64 = lambda t: t.to(device=device, dtype=torch.float64).contiguous()
         self.M = pack.M
+        self.K = int(pack.cluster_off[-1])       # sources in the pack
         self.ll, self.mm, self.nn1 = f64(pack.ll), f64(pack.mm), f64(pack.nn1)
         for k in ('sI', 'sQ', 'sU', 'sV', 'sI0', 'sQ0', 'sU0', 'sV0',
                   'spec_idx', 'spec_idx1', 'spec_idx2', 'eX', 'eY', 'eP'):
@@ -302,8 +303,62 @@ def gpu_pack(pack, device):
     return _gpu_pack_cache[key]
 
 
+_nsta_memo = {}      # (pairs token, version) -> (min, max) station index
+
+
+def _pair_range(pairs):
+    """(min, max) station index of a device pair table. Reads it back to
+    the host, so the answer is remembered per tensor."""
+    try:
+        key = (dispatch.obj_token(pairs), pairs._version)
+    except RuntimeError:                 # inference tensor: no version
+        key = None
+    hit = _nsta_memo.get(key)
+    if hit is None:
+        hit = (int(pairs.min()), int(pairs.max()))
+        if key is not None:
+            if len(_nsta_memo) > 64:
+                _nsta_memo.pop(next(iter(_nsta_memo)))
+            _nsta_memo[key] = hit
+    return hit
+
+
+def _check_ejones(ejones, beam, pairs, Nbase, R, K):
+    """Host-side contract of the E-Jones kernels, which index ejones and
+    beam by timeslot, source and station with no checks of their own.
+    Returns the station count N."""
+    if pairs is None:
+        raise ValueError("ejones needs the station-pair table `pairs`")
+    if ejones.dim() != 5 or tuple(ejones.shape[3:]) != (2, 2):
+        raise ValueError("ejones must be [T, K, NE, 2, 2], got "
+                         f"{tuple(ejones.shape)}")
+    Nbase = int(Nbase) or int(pairs.shape[0])
+    if pairs.dim() != 2 or pairs.shape[0] < Nbase or pairs.shape[1] != 2:
+        raise ValueError("pairs must be [Nbase, 2]")
+    T, Ke, NE = (int(x) for x in ejones.shape[:3])
+    if T * Nbase != R:
+        raise ValueError(f"ejones has {T} timeslots of {Nbase} baselines, "
+                         f"the predict has {R} rows")
+    if Ke < K:
+        raise ValueError(f"ejones covers {Ke} sources, the pack has {K}")
+    lo, hi = _pair_range(pairs)
+    if beam is not None:
+        if tuple(beam.shape[:2]) != (T, Ke):
+            raise ValueError("beam and ejones disagree on [T, K]")
+        N = int(beam.shape[2])
+    else:
+        N = NE if NE != 1 else hi + 1
+    if lo < 0 or hi >= N:
+        raise ValueError(f"pairs name stations {lo}..{hi}, outside the "
+                         f"{N} stations of the beam buffers")
+    if NE not in (1, N):
+        raise ValueError(f"ejones holds {NE} patterns per source; must be "
+                         f"1 or the station count {N}")
+    return N
+
+
 def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
-                beam=None, pairs=None, Nbase=0, **kw):
+                beam=None, pairs=None, Nbase=0, ejones=None, **kw):
     """Kernel-backed coherency predict. Optional fused station beam
     (-B 1, reference DOBEAM_ARRAY): `beam` [T, K, N] float32 real
     array-factor gains on device + `pairs` [Nbase, 2] int32 — each
@@ -312,22 +367,43 @@ def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
     (gp.sh) are added by k_shapelet_coh on the same stream, beam-scaled
     the same way; once the pack is on the device this path has no host
     synchronisation. SAGECAL_SHAPELET_HOST=1 swaps that kernel for its
-    torch mirror shapelet_coh_torch."""
+    torch mirror shapelet_coh_torch.
+
+    Optional element beam (-B 2/3, DOBEAM_FULL / DOBEAM_ELEMENT): `ejones`
+    [T, K, NE, 2, 2] complex64, NE = 1 (one dipole pattern per array
+    origin) or N (one per station). Each source then contributes
+    g_p g_q E_p C E_q^H with E_s = ejones[t, k, s if NE == N else 0] and
+    g = beam[t,k,.] (1 without `beam`), through the _ej variants of both
+    kernels. `pairs` is required with it. The first call with a new pair
+    table reads its index range back for the bounds check."""
     gp = pack if isinstance(pack, GPUPack) else gpu_pack(pack, u.device)
     sI, sQ, sU, sV = gp.fluxes_at(freq, freq0)
     r1 = gp.r1_for(dec0)
     u64 = u.to(torch.float64).contiguous()
     v64 = v.to(torch.float64).contiguous()
     w64 = w.to(torch.float64).contiguous()
-    if beam is not None:
-        beam = beam.to(device=u.device, dtype=torch.float32).contiguous()
-        pairs = pairs.to(device=u.device, dtype=torch.int32).contiguous()
+    Nsta = 0
+    if ejones is not None:
+        if os.environ.get('SAGECAL_SHAPELET_HOST') == '1' \
+                and gp.sh is not None:
+            raise RuntimeError("the torch shapelet mirror has no E-Jones")
+        Nsta = _check_ejones(ejones, beam, pairs, Nbase, int(u.shape[0]),
+                             gp.K)
+        ejones = ejones.to(device=u.device,
+                           dtype=torch.complex64).contiguous()
+    if beam is not None or ejones is not None:
+        if beam is not None:
+            beam = beam.to(device=u.device,
+                           dtype=torch.float32).contiguous()
         Nbase = int(Nbase) or int(pairs.shape[0])
+        pairs = pairs[:Nbase].to(device=u.device,
+                                 dtype=torch.int32).contiguous()
+    ej = {} if ejones is None else {'ejones': ejones, 'Nsta': Nsta}
     out = _ext().predict_coh(
         u64, v64, w64, gp.ll, gp.mm, gp.nn1, sI, sQ, sU, sV,
         gp.eX, gp.eY, gp.eP, gp.cxi, gp.sxi, gp.cphi, gp.sphi, r1,
         gp.stype, gp.cluster_off, float(freq), float(fdelta) * 0.5,
-        float(tdelta), beam=beam, pairs=pairs, Nbase=int(Nbase))
+        float(tdelta), beam=beam, pairs=pairs, Nbase=int(Nbase), **ej)
     if gp.sh is not None:
         tab = gp.sh
         flux = gp.shapelet_fluxes_at(freq, freq0)
@@ -344,8 +420,43 @@ def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
             _ext().shapelet_coh_add(
                 out, u64, v64, w64, *(getattr(tab, k) for k in tab.FIELDS),
                 flux, r1s, float(freq), float(fdelta) * 0.5, float(tdelta),
-                beam=beam, pairs=pairs, Nbase=int(Nbase))
+                beam=beam, pairs=pairs, Nbase=int(Nbase), **ej)
     return out.view(gp.M, -1, 2, 2)
+
+
+def array_beam_gains(elem, nelem, du, below, freq):
+    """Station array-factor gains on the device (k_array_beam):
+      gain[t,k,n] = below[t,k] ? 0
+                  : |(1/nelem[n]) sum_e exp(i 2 pi f/c elem[n,e] . du[t,k])|
+    elem [N, Emax, 3] float64 ENU offsets, zero-padded, on the device the
+    gains are wanted on; nelem [N] element counts, each >= 1; du [T, K, 3]
+    float64 source minus pointing direction; below [T, K] bool/uint8.
+    Returns [T, K, N] float32, the `beam` argument of predict_coh."""
+    import numpy as np
+    from ..constants import C_LIGHT
+    if not torch.is_tensor(elem) or not elem.is_cuda:
+        raise ValueError("elem must be a device tensor [N, Emax, 3]")
+    if elem.dim() != 3 or elem.shape[2] != 3 or elem.shape[1] < 1:
+        raise ValueError("elem must be [N, Emax, 3]")
+    dev = elem.device
+    N, Emax = int(elem.shape[0]), int(elem.shape[1])
+    ne = np.asarray(nelem.cpu() if torch.is_tensor(nelem) else nelem)
+    if ne.shape != (N,):
+        raise ValueError(f"nelem must be [{N}]")
+    if (ne < 1).any() or (ne > Emax).any():
+        raise ValueError("every station needs 1 <= nelem <= Emax elements, "
+                         f"got {ne.tolist()}")
+    du = torch.as_tensor(du)
+    below = torch.as_tensor(below)
+    if du.dim() != 3 or du.shape[2] != 3 \
+            or tuple(below.shape) != tuple(du.shape[:2]):
+        raise ValueError("du must be [T, K, 3] and below [T, K]")
+    return _ext().array_beam_gains(
+        elem.to(torch.float64).contiguous(),
+        torch.as_tensor(ne.astype(np.int32)).to(dev),
+        du.to(device=dev, dtype=torch.float64).contiguous(),
+        below.to(device=dev, dtype=torch.uint8).contiguous(),
+        2.0 * math.pi * float(freq) / C_LIGHT)
 
 
 class BaselineLayout:
