@@ -119,14 +119,18 @@ def load_context(args):
     return ms, pack, clusters, device, dtype
 
 
+def _beam_key(pack, tmjd):
+    from ..ops import dispatch
+    return (dispatch.obj_token(pack), tuple(np.atleast_1d(tmjd).tolist()))
+
+
 def _beam_geometry(pack, tile, cfg, tmjd):
     """Source/pointing geometry of one tile, built once and kept on the
     tile: the per-channel predicts of -B 4/5/6 and of the beamed residuals
     all share it."""
     from .. import beams
     memo = getattr(tile, '_beam_geom', None)
-    from ..ops import dispatch
-    key = (dispatch.obj_token(pack), tuple(np.atleast_1d(tmjd).tolist()))
+    key = _beam_key(pack, tmjd)
     if memo is None or memo[0] != key:
         ra, dec = beams._pack_radec(pack, tile.dec0)
         memo = (key, beams.beam_geometry(cfg, ra, dec, tmjd))
@@ -137,29 +141,77 @@ def _beam_geometry(pack, tile, cfg, tmjd):
     return memo[1]
 
 
-def _predict_with_beam(ms, pack, tile, ti, args):
-    """Coherencies with the station array beam applied (-B 1;
-    predict_visibilities_multifreq_withbeam role). The MS must carry the
-    element layout: NpzMS key `element_enu` [N, E, 3] (m) plus optional
-    `lon`/`lat` (rad) — the analog of the LOFAR ANTENNA_FIELD tables the
-    reference reads (data.cpp:268-288)."""
+def _beam_config(ms):
+    """(ArrayConfig, tmjd0, z) from the beam keys of the MS (docs/FORMATS.md,
+    the analog of the LOFAR ANTENNA_FIELD tables the reference reads,
+    data.cpp:268-288). `tile_enu` present means a two-stage HBA station
+    with `element_enu` holding the tile centroids, as data.cpp picks
+    STAT_TILE for every HBA measurement set."""
     from .. import beams
     z = getattr(ms, '_z', {})
-    if 'element_enu' not in z:
-        raise SystemExit(
-            "-B 1 requires element layouts in the MS (key 'element_enu')")
     lon = float(z['lon']) if 'lon' in z else 0.0
     lat = float(z['lat']) if 'lat' in z else 0.92
+    kw = {}
+    if 'tile_enu' in z:
+        kw = dict(
+            bf_type='tile', tile_enu=np.asarray(z['tile_enu']),
+            tile_ra0=float(z['tile_ra0']) if 'tile_ra0' in z else None,
+            tile_dec0=float(z['tile_dec0']) if 'tile_dec0' in z else None)
     cfg = beams.ArrayConfig(list(np.asarray(z['element_enu'])), lon, lat,
-                            ms.ra0, ms.dec0)
-    T = ms.tilesz
+                            ms.ra0, ms.dec0, **kw)
     t0 = float(z['tmjd0']) if 'tmjd0' in z else 56789.0
-    tmjd = t0 + (ti * T + np.arange(T) + 0.5) * ms.tdelta / 86400.0
-    mode = args.dobeam
+    return cfg, t0, z
+
+
+def _channel_gains(pack, tile, cfg, geom, tmjd, freq):
+    """Two-stage station gains [T, K, N] of one channel of the tile. The
+    gains of ALL the tile's channels come from one batched call, made once
+    per tile and kept on it next to the geometry; a frequency that is not
+    one of the tile's channels is evaluated on its own. None for a
+    single-stage config, whose callers compute their gains as before."""
+    from .. import beams
+    if cfg.bf_type != 'tile':
+        return None
+    freqs = tuple(float(f) for f in tile.freqs)
+    if float(freq) not in freqs:
+        return beams.station_beam_gains(cfg, geom, [float(freq)],
+                                        tile.u.device)[0]
+    # the key names the sources, the times and the channels, not the
+    # config: like _beam_geom it relies on one MS giving one config, so
+    # tile_enu and the tile pointing cannot change under a tile
+    key = _beam_key(pack, tmjd) + (freqs,)
+    memo = getattr(tile, '_beam_gains', None)
+    if memo is None or memo[0] != key:
+        memo = (key, beams.station_beam_gains(cfg, geom, freqs,
+                                              tile.u.device))
+        try:
+            tile._beam_gains = memo
+        except AttributeError:
+            pass
+    return memo[1][freqs.index(float(freq))]
+
+
+def _elem_coeffs(args, z):
     et = getattr(args, 'elem_type', 'auto')
     if et == 'auto':
         et = str(z['elem_type']) if 'elem_type' in z else 'synthetic'
-    coeffs = None if et == 'synthetic' else et   # name -> LOFAR tables
+    return None if et == 'synthetic' else et     # name -> LOFAR tables
+
+
+def _predict_with_beam(ms, pack, tile, ti, args):
+    """Coherencies with the station beam applied (-B 1..6;
+    predict_visibilities_multifreq_withbeam role). The MS must carry the
+    element layout: NpzMS key `element_enu` [N, E, 3] (m) plus optional
+    `lon`/`lat` (rad) and, for two-stage HBA stations, `tile_enu`."""
+    from .. import beams
+    if 'element_enu' not in getattr(ms, '_z', {}):
+        raise SystemExit(
+            "-B 1 requires element layouts in the MS (key 'element_enu')")
+    cfg, t0, z = _beam_config(ms)
+    T = ms.tilesz
+    tmjd = t0 + (ti * T + np.arange(T) + 0.5) * ms.tdelta / 86400.0
+    mode = args.dobeam
+    coeffs = _elem_coeffs(args, z)
     geom = _beam_geometry(pack, tile, cfg, tmjd)
     if mode <= 3:
         return beams.predict_coh_withbeam(
@@ -173,11 +225,13 @@ def _predict_with_beam(ms, pack, tile, ti, args):
     fdelta_ch = tile.fdelta / len(tile.freqs)
     acc = None
     for f in tile.freqs:
+        gains = _channel_gains(pack, tile, cfg, geom, tmjd, f) \
+            if mode in (1, 2) else None
         c = beams.predict_coh_withbeam(
             pack, tile.u, tile.v, tile.w, float(f), tile.freq0,
             fdelta_ch, tile.tdelta, tile.dec0, cfg, tmjd,
             ms.bb_tensor(), ms.Nbase, T, mode=mode, coeffs=coeffs,
-            geom=geom)
+            geom=geom, gains=gains)
         acc = c if acc is None else acc + c
     return acc / len(tile.freqs)
 
@@ -187,26 +241,19 @@ def _predict_channel_with_beam(ms, pack, tile, ti, args, freq,
     """One channel's beamed coherencies for the residual path (-B with
     multifreq residuals)."""
     from .. import beams
-    z = getattr(ms, '_z', {})
-    lon = float(z['lon']) if 'lon' in z else 0.0
-    lat = float(z['lat']) if 'lat' in z else 0.92
-    cfg = beams.ArrayConfig(list(np.asarray(z['element_enu'])), lon, lat,
-                            ms.ra0, ms.dec0)
+    cfg, t0, z = _beam_config(ms)
     T = ms.tilesz
-    t0 = float(z['tmjd0']) if 'tmjd0' in z else 56789.0
     tmjd = t0 + (ti * T + np.arange(T) + 0.5) * ms.tdelta / 86400.0
     mode = args.dobeam
     if mode > 3:
         mode -= 3
-    et = getattr(args, 'elem_type', 'auto')
-    if et == 'auto':
-        et = str(z['elem_type']) if 'elem_type' in z else 'synthetic'
-    coeffs = None if et == 'synthetic' else et
+    geom = _beam_geometry(pack, tile, cfg, tmjd)
+    gains = _channel_gains(pack, tile, cfg, geom, tmjd, freq) \
+        if mode in (1, 2) else None
     return beams.predict_coh_withbeam(
         pack, tile.u, tile.v, tile.w, freq, tile.freq0, fdelta_ch,
         tile.tdelta, tile.dec0, cfg, tmjd, ms.bb_tensor(), ms.Nbase, T,
-        mode=mode, coeffs=coeffs,
-        geom=_beam_geometry(pack, tile, cfg, tmjd))
+        mode=mode, coeffs=_elem_coeffs(args, z), geom=geom, gains=gains)
 
 
 def uv_flags(tile, args):

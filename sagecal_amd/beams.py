@@ -32,18 +32,60 @@ class ArrayConfig:
     """Per-station element layout + beam pointing (LOFAR_ANTENNA_FIELD
     analog, data.cpp:268-288)."""
 
+    MAX_TILE_DIPOLES = 64
+
     def __init__(self, element_enu, lon, lat, b_ra0, b_dec0,
-                 tile_enu=None, freq0_tile=None):
+                 tile_enu=None, freq0_tile=None, bf_type='single',
+                 tile_ra0=None, tile_dec0=None):
         # element_enu: list of [K_s, 3] arrays (per station) or one shared
         self.element_enu = element_enu
         self.lon, self.lat = lon, lat
         self.b_ra0, self.b_dec0 = b_ra0, b_dec0
         self.tile_enu = tile_enu        # dipole offsets within a tile (HBA)
         self.freq0_tile = freq0_tile
+        # bf_type 'single': every element is a dipole steered at
+        # (b_ra0, b_dec0) (STAT_SINGLE). 'tile': two-stage HBA beamformer
+        # (STAT_TILE, stationbeam.c:114): element_enu holds the tile
+        # centroids, steered at (b_ra0, b_dec0); tile_enu the D dipole
+        # offsets inside a tile, [D, 3] shared or per station ([N, D, 3] or
+        # a list), steered at the tile pointing (tile_ra0, tile_dec0).
+        # tile_enu alone does not switch the type: only tile_beam reads it
+        # on a 'single' config.
+        if bf_type not in ('single', 'tile'):
+            raise ValueError(f"bf_type must be 'single' or 'tile', "
+                             f"got {bf_type!r}")
+        self.bf_type = bf_type
+        self.tile_ra0 = b_ra0 if tile_ra0 is None else tile_ra0
+        self.tile_dec0 = b_dec0 if tile_dec0 is None else tile_dec0
+        if bf_type == 'tile':
+            if tile_enu is None:
+                raise ValueError("bf_type='tile' needs tile_enu, the dipole "
+                                 "offsets inside a tile")
+            nsta = len(element_enu) if isinstance(element_enu,
+                                                  (list, tuple)) else 1
+            self.tile_dipoles(nsta)     # shape errors surface here
 
     def elements(self, s):
         e = self.element_enu
         return e[s] if isinstance(e, (list, tuple)) else e
+
+    def tile_dipoles(self, nsta):
+        """Dipole offsets inside a tile for stations 0..nsta-1:
+        [nsta, D, 3] float64, a shared [D, 3] layout repeated."""
+        t = self.tile_enu
+        if isinstance(t, (list, tuple)):
+            t = np.stack([np.asarray(x, dtype=np.float64) for x in t])
+        t = np.asarray(t, dtype=np.float64)
+        if t.ndim == 2:
+            t = np.broadcast_to(t, (nsta,) + t.shape)
+        if t.ndim != 3 or t.shape[2] != 3 or t.shape[0] != nsta:
+            raise ValueError("tile_enu must be [D, 3] or one [D, 3] per "
+                             f"station ({nsta}), got {t.shape}")
+        if not 1 <= t.shape[1] <= self.MAX_TILE_DIPOLES:
+            raise ValueError("a tile holds 1 to "
+                             f"{self.MAX_TILE_DIPOLES} dipoles, "
+                             f"got {t.shape[1]}")
+        return np.ascontiguousarray(t)
 
 
 def _direction_enu(ra, dec, lon, lat, gmst):
@@ -61,10 +103,13 @@ class BeamGeometry:
       du    [T, K, 3] float64  ENU unit vector of the source minus that of
                                the beam pointing
       below [T, K]    bool     source under the horizon (el < 0)
-      az,el [T, K]    float64  source azimuth and elevation (rad)"""
+      az,el [T, K]    float64  source azimuth and elevation (rad)
+      du_tile [T, K, 3] float64  like du, minus the direction of the tile
+                               pointing; only for a two-stage config"""
 
-    def __init__(self, du, below, az, el):
+    def __init__(self, du, below, az, el, du_tile=None):
         self.du, self.below, self.az, self.el = du, below, az, el
+        self.du_tile = du_tile
         self.T, self.K = below.shape
 
 
@@ -74,17 +119,27 @@ def beam_geometry(cfg, ra, dec, tmjd):
     element pattern, done once."""
     ra = np.atleast_1d(ra)
     gmst = coords.jd_to_gmst(np.asarray(np.atleast_1d(tmjd)) + 2400000.5)
-    dus, azs, els = [], [], []
+    two = getattr(cfg, 'bf_type', 'single') == 'tile'
+    dus, dts, azs, els = [], [], [], []
     for g in np.atleast_1d(gmst):
         usrc, az, el = _direction_enu(ra, dec, cfg.lon, cfg.lat, g)
-        upnt, _, _ = _direction_enu(cfg.b_ra0, cfg.b_dec0, cfg.lon,
-                                    cfg.lat, g)
+        if two:
+            # both pointings in one call: the loop is host time per slot
+            upnt, _, _ = _direction_enu([cfg.b_ra0, cfg.tile_ra0],
+                                        [cfg.b_dec0, cfg.tile_dec0],
+                                        cfg.lon, cfg.lat, g)
+            dts.append(usrc - upnt[1])
+            upnt = upnt[0]
+        else:
+            upnt, _, _ = _direction_enu(cfg.b_ra0, cfg.b_dec0, cfg.lon,
+                                        cfg.lat, g)
         dus.append(usrc - upnt)                        # [K, 3]
         azs.append(az)
         els.append(el)
     el = np.stack(els)
     return BeamGeometry(np.stack(dus).astype(np.float64), el < 0,
-                        np.stack(azs), el)
+                        np.stack(azs), el,
+                        np.stack(dts).astype(np.float64) if two else None)
 
 
 def array_beam(cfg, ra, dec, freqs, tmjd, station_ids=None, device='cpu'):
@@ -384,25 +439,90 @@ def array_beam_gains(cfg, geom, freq, device='cpu'):
     buffer of the predict kernels (beamgain, stationbeam.c:318). On a CUDA
     device they come from k_array_beam (float32); on the CPU from the fp64
     torch array factor, array_beam(...)[..., 0].abs() permuted (float64).
-    A one-element station has gain exactly 1 above the horizon."""
-    elem_list = [np.asarray(e, dtype=np.float64).reshape(-1, 3)
-                 for e in _station_elements(cfg)]
-    nelem = np.array([e.shape[0] for e in elem_list])
+    A one-element station has gain exactly 1 above the horizon.
+
+    For a two-stage config (bf_type 'tile') this is the product of the
+    tile-centroid factor and the dipole-in-tile factor, row 0 of
+    station_beam_gains at [freq] (k_station_beam on a CUDA device)."""
+    if _is_tile(cfg):
+        return station_beam_gains(cfg, geom, [freq], device)[0]
+    elem_list, nelem = _element_lists(cfg)
     if torch.device(device).type == 'cuda':
         from .ops import hip_host
-        if (nelem < 1).any():
-            raise ValueError("every station needs at least one element")
-        elem = np.zeros((len(elem_list), int(nelem.max()), 3))
-        for n, e in enumerate(elem_list):
-            elem[n, :e.shape[0]] = e
         return hip_host.array_beam_gains(
-            torch.as_tensor(elem).to(device), nelem, geom.du, geom.below,
-            freq)
+            torch.as_tensor(_padded_elements(elem_list, nelem)).to(device),
+            nelem, geom.du, geom.below, freq)
     af = _array_factor(cfg, geom, [freq], None, device)  # [S, K, T, 1]
     g = af[..., 0].abs().permute(2, 1, 0).contiguous()   # [T, K, S]
     one = torch.as_tensor(nelem == 1, device=g.device)
     up = ~torch.as_tensor(geom.below, device=g.device)
     g[up[:, :, None] & one[None, None, :]] = 1.0
+    return g
+
+
+def _is_tile(cfg):
+    return getattr(cfg, 'bf_type', 'single') == 'tile'
+
+
+def _element_lists(cfg):
+    elem_list = [np.asarray(e, dtype=np.float64).reshape(-1, 3)
+                 for e in _station_elements(cfg)]
+    return elem_list, np.array([e.shape[0] for e in elem_list])
+
+
+def _padded_elements(elem_list, nelem):
+    """[N, Emax, 3] zero-padded element table of the device kernels."""
+    if (nelem < 1).any():
+        raise ValueError("every station needs at least one element")
+    elem = np.zeros((len(elem_list), int(nelem.max()), 3))
+    for n, e in enumerate(elem_list):
+        elem[n, :e.shape[0]] = e
+    return elem
+
+
+def station_beam_gains(cfg, geom, freqs, device='cpu'):
+    """Real station beam gains [F, T, K, N] at every frequency of `freqs`
+    in one call; row f is the `beam` buffer of the predict kernels at
+    freqs[f]. Single-stage configs give the array factor of
+    array_beam_gains; two-stage configs (bf_type 'tile', arraybeam
+    STAT_TILE, stationbeam.c:114-176 with the beamformer frequency equal to
+    the evaluation frequency):
+      gain[f,t,k,n] = below[t,k] ? 0
+        : |mean_c exp(i kf cent[n,c] . du[t,k])|
+          * |mean_d exp(i kf dip[n,d] . du_tile[t,k])|
+    with kf = 2 pi freqs[f] / c, cent = element_enu (tile centroids) and
+    dip = tile_enu. On a CUDA device one k_station_beam launch (float32);
+    on the CPU fp64 torch. A one-tile station has centroid factor exactly
+    1 above the horizon."""
+    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    two = _is_tile(cfg)
+    elem_list, nelem = _element_lists(cfg)
+    if two and geom.du_tile is None:
+        raise ValueError("the geometry was built for a single-stage config: "
+                         "it carries no du_tile")
+    dip = cfg.tile_dipoles(len(elem_list)) if two else None
+    if torch.device(device).type == 'cuda':
+        from .ops import hip_host
+        kw = dict(tile=torch.as_tensor(dip).to(device),
+                  du_tile=geom.du_tile) if two else {}
+        return hip_host.station_beam_gains(
+            torch.as_tensor(_padded_elements(elem_list, nelem)).to(device),
+            nelem, geom.du, geom.below, freqs, **kw)
+    af = _array_factor(cfg, geom, freqs, None, device)   # [S, K, T, F]
+    g = af.abs().permute(3, 2, 1, 0).contiguous()        # [F, T, K, S]
+    up = ~torch.as_tensor(geom.below, device=g.device)
+    one = torch.as_tensor(nelem == 1, device=g.device)
+    g[:, up[:, :, None] & one[None, None, :]] = 1.0
+    if two:
+        d = torch.as_tensor(dip, dtype=torch.float64, device=device)
+        dt = torch.as_tensor(geom.du_tile, dtype=torch.float64,
+                             device=device)
+        fq = torch.as_tensor(freqs, dtype=torch.float64, device=device)
+        proj = torch.einsum('ndx,tkx->tknd', d, dt)
+        ph = proj.unsqueeze(0) * ((2.0 * math.pi / C_LIGHT)
+                                  * fq)[:, None, None, None, None]
+        tf = torch.complex(torch.cos(ph), torch.sin(ph)).mean(dim=-1).abs()
+        g = g * tf                                       # below stays 0
     return g
 
 
@@ -432,7 +552,7 @@ def element_jones(coeffs, geom, freq):
 
 def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
                          cfg, tmjd, bb, Nbase, T, mode=1, coeffs=None,
-                         geom=None):
+                         geom=None, gains=None):
     """Coherencies with the station beam applied per source/station
     (precalculate_coherencies_withbeam semantics, Dirac_radio.h:471):
     C'_pq(src) = g_p(src) C g_q(src)^* for the scalar array factor
@@ -446,14 +566,22 @@ def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
 
     On a GPU tensor every mode is ONE hip_host.predict_coh call
     (kernel_array_beam / kernel_element_beam -> kernel_coherencies
-    structure): the gains of modes 1 and 2 come from k_array_beam, the
-    host-evaluated element E-Jones of modes 2 and 3 is applied per source
-    inside the predict kernels. On the CPU the per-source torch loop
-    below is the fp64 yardstick for that path.
+    structure): the gains of modes 1 and 2 come from k_array_beam
+    (k_station_beam for a two-stage config), the host-evaluated element
+    E-Jones of modes 2 and 3 is applied per source inside the predict
+    kernels. On the CPU the per-source torch loop below is the fp64
+    yardstick for that path.
 
     `geom`: the BeamGeometry of (pack, cfg, tmjd) when the caller already
     has it (per-channel loops build it once per tile); it does not change
     the result.
+
+    Modes 1 and 2 honour the config's beamformer type: a two-stage config
+    (bf_type 'tile') applies the tile-centroid times dipole-in-tile gains
+    of station_beam_gains. `gains`: those gains [T, K, N] at `freq` when the
+    caller already has them (one row of a station_beam_gains batch); used
+    in modes 1 and 2 in place of computing them here. Mode 3 does not
+    depend on the beamformer type (stationbeam.c:324-352).
     """
     from .ops import reference as R
     B = u.shape[0]
@@ -473,14 +601,22 @@ def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
     if u.is_cuda and (use_array or use_elem):
         # device path: no per-source loop; a missing extension raises
         from .ops import hip_host
-        beam_t = array_beam_gains(cfg, geom, freq, u.device) \
-            if use_array else None
+        beam_t = None
+        if use_array:
+            beam_t = array_beam_gains(cfg, geom, freq, u.device) \
+                if gains is None else \
+                gains.to(device=u.device, dtype=torch.float32)
         ej = element_jones(coeffs, geom, freq).to(torch.complex64) \
             .unsqueeze(2).to(u.device) if use_elem else None
         return hip_host.predict_coh(
             pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
             beam=beam_t, pairs=bb, Nbase=Nbase, ejones=ej).to(cdtype)
-    if use_array:
+    if use_array and (gains is not None or _is_tile(cfg)):
+        if gains is None:
+            gains = array_beam_gains(cfg, geom, freq, 'cpu')
+        af = gains.to(device=u.device, dtype=torch.float64) \
+            .permute(2, 1, 0)                        # [S, K, T] real
+    elif use_array:
         af = _array_factor(cfg, geom, [freq])        # [S, K, T, 1]
         af = af[..., 0].abs()                        # [S, K, T] real
     out = torch.zeros(M, B, 2, 2, dtype=cdtype, device=u.device)

@@ -14,6 +14,9 @@ hipError_t launch_predict_coh(const double*, const double*, const double*,
     float2*, hipStream_t);
 hipError_t launch_array_beam(const double*, const int*, const double*,
     const unsigned char*, int, int, int, double, float*, hipStream_t);
+hipError_t launch_station_beam(const double*, const int*, const double*,
+    const double*, const double*, const unsigned char*, const double*, int,
+    int, int, int, int, float*, hipStream_t);
 hipError_t launch_shapelet_coh(const double*, const double*, const double*,
     int, int, const int*, const int*, const int*, const float*, const int*,
     const float*, const float*, const float*, const float*, const float*,
@@ -250,6 +253,67 @@ torch::Tensor array_beam_gains(
   return gain;
 }
 
+// gain[f,t,k,n] of k_station_beam. elem, nelem, du and below as for
+// array_beam_gains; kf [F] float64 wavenumbers 2 pi f / c; tile [N, D, 3]
+// float64 dipole offsets inside a tile and du_tile [T, K, 3] float64, given
+// together (two-stage) or not at all (single stage), 1 <= D <= 64.
+// Returns [F, T, K, N] float32.
+torch::Tensor station_beam_gains(
+    torch::Tensor elem, torch::Tensor nelem, torch::Tensor du,
+    torch::Tensor below, torch::Tensor kf,
+    c10::optional<torch::Tensor> tile, c10::optional<torch::Tensor> du_tile) {
+  TORCH_CHECK(elem.is_cuda() && elem.scalar_type() == torch::kDouble &&
+              elem.is_contiguous() && elem.dim() == 3 && elem.size(2) == 3 &&
+              elem.size(1) > 0, "elem must be contiguous [N, Emax, 3] float64");
+  const int64_t N = elem.size(0), Emax = elem.size(1);
+  TORCH_CHECK(nelem.device() == elem.device() &&
+              nelem.scalar_type() == torch::kInt && nelem.is_contiguous() &&
+              nelem.numel() == N, "nelem must be contiguous [N] int32");
+  TORCH_CHECK(du.device() == elem.device() &&
+              du.scalar_type() == torch::kDouble && du.is_contiguous() &&
+              du.dim() == 3 && du.size(2) == 3,
+              "du must be contiguous [T, K, 3] float64");
+  const int64_t T = du.size(0), K = du.size(1);
+  TORCH_CHECK(below.device() == elem.device() &&
+              below.scalar_type() == torch::kByte && below.is_contiguous() &&
+              below.dim() == 2 && below.size(0) == T && below.size(1) == K,
+              "below must be contiguous [T, K] uint8");
+  TORCH_CHECK(kf.device() == elem.device() &&
+              kf.scalar_type() == torch::kDouble && kf.is_contiguous() &&
+              kf.dim() == 1, "kf must be contiguous [F] float64");
+  const int64_t F = kf.size(0);
+  TORCH_CHECK(T * K < (int64_t(1) << 31), "too many (timeslot, source) pairs");
+  TORCH_CHECK(tile.has_value() == du_tile.has_value(),
+              "tile and du_tile come together");
+  const double* tile_p = nullptr;
+  const double* dut_p = nullptr;
+  int64_t D = 0;
+  if (tile.has_value()) {
+    const torch::Tensor& tl = *tile;
+    const torch::Tensor& dt = *du_tile;
+    TORCH_CHECK(tl.device() == elem.device() &&
+                tl.scalar_type() == torch::kDouble && tl.is_contiguous() &&
+                tl.dim() == 3 && tl.size(0) == N && tl.size(2) == 3 &&
+                tl.size(1) >= 1 && tl.size(1) <= 64,
+                "tile must be contiguous [N, D, 3] float64, 1 <= D <= 64");
+    TORCH_CHECK(dt.device() == elem.device() &&
+                dt.scalar_type() == torch::kDouble && dt.is_contiguous() &&
+                dt.dim() == 3 && dt.size(0) == T && dt.size(1) == K &&
+                dt.size(2) == 3,
+                "du_tile must be contiguous [T, K, 3] float64");
+    D = tl.size(1);
+    tile_p = tl.data_ptr<double>();
+    dut_p = dt.data_ptr<double>();
+  }
+  auto gain = torch::empty({F, T, K, N},
+      torch::dtype(torch::kFloat).device(elem.device()));
+  CHECK_HIP(launch_station_beam(elem.data_ptr<double>(),
+      nelem.data_ptr<int>(), tile_p, du.data_ptr<double>(), dut_p,
+      below.data_ptr<uint8_t>(), kf.data_ptr<double>(), (int)N, (int)Emax,
+      (int)D, (int)(T * K), (int)F, gain.data_ptr<float>(), cur_stream()));
+  return gain;
+}
+
 std::vector<torch::Tensor> jtj_jtr(
     torch::Tensor x, torch::Tensor coh, torch::Tensor J,
     torch::Tensor pairs, torch::Tensor chunk_tab, torch::Tensor pidx,
@@ -413,6 +477,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("array_beam_gains", &array_beam_gains,
         "station array-factor gains [T, K, N] (gfx950)", py::arg("elem"),
         py::arg("nelem"), py::arg("du"), py::arg("below"), py::arg("kf"));
+  m.def("station_beam_gains", &station_beam_gains,
+        "single- or two-stage station beam gains [F, T, K, N] (gfx950)",
+        py::arg("elem"), py::arg("nelem"), py::arg("du"), py::arg("below"),
+        py::arg("kf"), py::arg("tile") = py::none(),
+        py::arg("du_tile") = py::none());
   m.def("jtj_jtr", &jtj_jtr, "fused JtJ/Jtr assembly (gfx950)");
   m.def("model_cost", &model_cost, "per-chunk model cost (gfx950)");
   m.def("apply_jones", &apply_jones, "model apply / residual (gfx950)");

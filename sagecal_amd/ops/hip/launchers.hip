@@ -80,6 +80,28 @@ hipError_t launch_array_beam(
   return hipGetLastError();
 }
 
+// tile and du_tile come together or not at all (single stage); D counts
+// the dipoles of a tile and is ignored without them
+hipError_t launch_station_beam(
+    const double* elem, const int* nelem, const double* tile,
+    const double* du, const double* du_tile, const unsigned char* below,
+    const double* kfs, int N, int Emax, int D, int TK, int F, float* gain,
+    hipStream_t stream) {
+  if (N <= 0 || TK <= 0 || F <= 0) return hipSuccess;
+  if (Emax <= 0 || (tile == nullptr) != (du_tile == nullptr))
+    return hipErrorInvalidValue;
+  if (tile != nullptr && (D < 1 || D > SB_DMAX)) return hipErrorInvalidValue;
+  const int tb = 256;
+  const long long gy = (N + SB_NSTA - 1) / SB_NSTA;
+  const long long gz = (F + SB_NF - 1) / SB_NF;
+  if (gy > 65535 || gz > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_station_beam,
+      dim3((TK + tb - 1) / tb, (unsigned)gy, (unsigned)gz), dim3(tb), 0,
+      stream, elem, nelem, tile, du, du_tile, below, kfs, N, Emax, D, TK, F,
+      gain);
+  return hipGetLastError();
+}
+
 hipError_t launch_jtj_accum(
     const float2* x, const float2* coh, const float2* J, const int* pairs,
     const int* chunk_tab, const int* pidx, const float* wts, int Nbase,

@@ -480,3 +480,155 @@ k_array_beam(const double* __restrict__ elem,   // [N, Emax, 3] ENU, padded
       if (n0 + j < N) gain[(size_t)tk * N + n0 + j] = g[j];
   }
 }
+
+// Station beam gains of every station toward every (timeslot, source) at F
+// wavenumbers in one launch, single-stage or two-stage (HBA: an analogue
+// tile beam of D dipoles times the digital beam of the tile centroids;
+// arraybeam STAT_TILE, stationbeam.c:114; kernel_tile_array_beam role,
+// predict_model.cu:236):
+//   gain[f,t,k,n] = below[t,k] ? 0
+//     : |(1/nelem[n]) sum_e exp(i kf[f] elem[n,e] . du[t,k])|
+//       * |(1/D) sum_d exp(i kf[f] tile[n,d] . du_tile[t,k])|
+// The second factor is 1 when tile is null (single stage). The structure is
+// k_array_beam's: one thread per (t,k), SB_NSTA consecutive stations per
+// block, elements staged through LDS in tiles of AB_ETILE (any Emax), the
+// dipoles of a station in one pass (D <= SB_DMAX), and every sum taken in
+// element order, so results repeat bit for bit. Unlike k_array_beam the
+// fp64 dot product e . du is formed once per element WITHOUT kf and then
+// scaled by each of the SB_NF wavenumbers the thread carries; blockIdx.z
+// walks the frequency axis in passes of SB_NF. A frequency's sum reads only
+// its own kf, so its result does not depend on what shares the launch.
+//
+// SB_NF = 4: per frequency a thread keeps re and im of the running sum (2
+// VGPRs) and SB_NSTA finished gains (4); kf is block-uniform and sits in
+// SGPRs. So every carried frequency costs 6 VGPRs on top of the ~26 of the
+// two directions, the addresses and the fmod/sincos temporaries. Four
+// frequencies stay under 64 VGPRs (hipcc reports 50 VGPRs, 92 SGPRs, no
+// spills), the most a wave may hold with 8 waves per SIMD resident; the
+// loop is fmod + sincos latency chains with no loads to overlap them, so
+// those resident waves are what hides it. Eight frequencies would need
+// about 24 more VGPRs plus the temporaries of four more chains, by this
+// count (an estimate, not compiled) past the 64 that 8 waves per SIMD
+// allow, to save the 3 fp64 multiply-adds of the dot product, which at 4
+// frequencies are already a small part of the per-element work. F = 256
+// is 64 passes along blockIdx.z; a last pass with fewer than SB_NF
+// frequencies skips the missing ones. A one-element (one-dipole) stage has
+// factor 1 by definition.
+#define SB_NF 4
+#define SB_NSTA 4
+#define SB_DMAX 64
+
+// sum_i exp(i kf[j] (x[i] ux + y[i] uy + z[i] uz)) over nt LDS entries,
+// added to re[j], im[j] in entry order, for the nf <= SB_NF frequencies of
+// this pass; nf is block-uniform, so the test on it is a scalar branch
+__device__ __forceinline__ void sb_accum(const double* x, const double* y,
+                                         const double* z, int nt, double ux,
+                                         double uy, double uz, int nf,
+                                         const double (&kf)[SB_NF],
+                                         float (&re)[SB_NF],
+                                         float (&im)[SB_NF]) {
+  for (int i = 0; i < nt; ++i) {
+    const double d = x[i] * ux + y[i] * uy + z[i] * uz;
+#pragma unroll
+    for (int j = 0; j < SB_NF; ++j) {
+      if (j < nf) {
+        float s, c;
+        sincos_reduced(kf[j] * d, &s, &c);
+        re[j] += c;
+        im[j] += s;
+      }
+    }
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_station_beam(const double* __restrict__ elem,   // [N, Emax, 3] ENU, padded
+               const int* __restrict__ nelem,     // [N], 1 <= nelem <= Emax
+               const double* __restrict__ tile,   // [N, D, 3] or null
+               const double* __restrict__ du,     // [TK, 3]
+               const double* __restrict__ du_tile,  // [TK, 3], with tile
+               const unsigned char* __restrict__ below,  // [TK]
+               const double* __restrict__ kfs,    // [F]
+               int N, int Emax, int D, int TK, int F,
+               float* __restrict__ gain) {        // [F, TK, N]
+  __shared__ double ex[AB_ETILE], ey[AB_ETILE], ez[AB_ETILE];
+  __shared__ double tx[SB_DMAX], ty[SB_DMAX], tz[SB_DMAX];
+  const int tk = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = tk < TK;
+  const bool two = tile != nullptr;        // block-uniform
+  double ux = 0, uy = 0, uz = 0, vx = 0, vy = 0, vz = 0;
+  bool dark = true;
+  if (live) {
+    ux = du[3 * (size_t)tk];
+    uy = du[3 * (size_t)tk + 1];
+    uz = du[3 * (size_t)tk + 2];
+    if (two) {
+      vx = du_tile[3 * (size_t)tk];
+      vy = du_tile[3 * (size_t)tk + 1];
+      vz = du_tile[3 * (size_t)tk + 2];
+    }
+    dark = below[tk] != 0;
+  }
+  const int f0 = blockIdx.z * SB_NF;
+  const int nf = min(SB_NF, F - f0);       // block-uniform, >= 1
+  double kf[SB_NF];
+#pragma unroll
+  for (int j = 0; j < SB_NF; ++j) kf[j] = f0 + j < F ? kfs[f0 + j] : 0.0;
+  const int n0 = blockIdx.y * SB_NSTA;
+  float g[SB_NSTA][SB_NF];
+#pragma unroll
+  for (int s = 0; s < SB_NSTA; ++s) {
+#pragma unroll
+    for (int j = 0; j < SB_NF; ++j) g[s][j] = 0.f;
+    const int n = n0 + s;            // block-uniform
+    if (n < N) {
+      const int ne = nelem[n];
+      float re[SB_NF], im[SB_NF];
+#pragma unroll
+      for (int j = 0; j < SB_NF; ++j) re[j] = im[j] = 0.f;
+      for (int e0 = 0; e0 < ne; e0 += AB_ETILE) {
+        const int nt = min(AB_ETILE, ne - e0);
+        __syncthreads();
+        for (int i = threadIdx.x; i < nt; i += blockDim.x) {
+          const double* p = elem + ((size_t)n * Emax + e0 + i) * 3;
+          ex[i] = p[0]; ey[i] = p[1]; ez[i] = p[2];
+        }
+        __syncthreads();
+        if (dark) continue;
+        sb_accum(ex, ey, ez, nt, ux, uy, uz, nf, kf, re, im);
+      }
+      if (!dark) {
+#pragma unroll
+        for (int j = 0; j < SB_NF; ++j)
+          g[s][j] = ne == 1 ? 1.0f
+              : sqrtf(re[j] * re[j] + im[j] * im[j]) / (float)ne;
+      }
+      if (two) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < D; i += blockDim.x) {
+          const double* p = tile + ((size_t)n * D + i) * 3;
+          tx[i] = p[0]; ty[i] = p[1]; tz[i] = p[2];
+        }
+        __syncthreads();
+        if (!dark && D > 1) {
+#pragma unroll
+          for (int j = 0; j < SB_NF; ++j) re[j] = im[j] = 0.f;
+          sb_accum(tx, ty, tz, D, vx, vy, vz, nf, kf, re, im);
+#pragma unroll
+          for (int j = 0; j < SB_NF; ++j)
+            g[s][j] *= sqrtf(re[j] * re[j] + im[j] * im[j]) / (float)D;
+        }
+      }
+    }
+  }
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < SB_NF; ++j) {
+      if (f0 + j >= F) continue;
+      float* o = gain + ((size_t)(f0 + j) * TK + tk) * N + n0;
+#pragma unroll
+      for (int s = 0; s < SB_NSTA; ++s)
+        if (n0 + s < N) o[s] = g[s][j];
+    }
+  }
+}

@@ -459,6 +459,63 @@ def array_beam_gains(elem, nelem, du, below, freq):
         2.0 * math.pi * float(freq) / C_LIGHT)
 
 
+def station_beam_gains(elem, nelem, du, below, freqs, tile=None,
+                       du_tile=None):
+    """Station beam gains at F frequencies in one launch (k_station_beam),
+    single-stage or, with `tile` and `du_tile`, two-stage (HBA):
+      gain[f,t,k,n] = below[t,k] ? 0
+        : |(1/nelem[n]) sum_e exp(i 2 pi f/c elem[n,e] . du[t,k])|
+          * |(1/D) sum_d exp(i 2 pi f/c tile[n,d] . du_tile[t,k])|
+    elem, nelem, du, below as for array_beam_gains (elem then holds the tile
+    centroids); freqs [F] Hz; tile [N, D, 3] float64 dipole offsets inside
+    a tile, 1 <= D <= 64, on elem's device; du_tile [T, K, 3] source minus
+    tile pointing direction. Returns [F, T, K, N] float32; row f is
+    the `beam` argument of predict_coh at freqs[f]."""
+    import numpy as np
+    from ..constants import C_LIGHT
+    if not torch.is_tensor(elem) or not elem.is_cuda:
+        raise ValueError("elem must be a device tensor [N, Emax, 3]")
+    if elem.dim() != 3 or elem.shape[2] != 3 or elem.shape[1] < 1:
+        raise ValueError("elem must be [N, Emax, 3]")
+    dev = elem.device
+    N, Emax = int(elem.shape[0]), int(elem.shape[1])
+    ne = np.asarray(nelem.cpu() if torch.is_tensor(nelem) else nelem)
+    if ne.shape != (N,):
+        raise ValueError(f"nelem must be [{N}]")
+    if (ne < 1).any() or (ne > Emax).any():
+        raise ValueError("every station needs 1 <= nelem <= Emax elements, "
+                         f"got {ne.tolist()}")
+    du = torch.as_tensor(du)
+    below = torch.as_tensor(below)
+    if du.dim() != 3 or du.shape[2] != 3 \
+            or tuple(below.shape) != tuple(du.shape[:2]):
+        raise ValueError("du must be [T, K, 3] and below [T, K]")
+    fq = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    if fq.ndim != 1 or fq.size < 1:
+        raise ValueError("freqs must be [F], F >= 1")
+    if (tile is None) != (du_tile is None):
+        raise ValueError("tile and du_tile are given together or not at all")
+    kw = {}
+    if tile is not None:
+        if not torch.is_tensor(tile) or tile.device != dev:
+            raise ValueError("tile must be a tensor on elem's device")
+        if tile.dim() != 3 or tuple(tile.shape[::2]) != (N, 3) \
+                or not 1 <= tile.shape[1] <= 64:
+            raise ValueError(f"tile must be [{N}, D, 3] with 1 <= D <= 64")
+        du_tile = torch.as_tensor(du_tile)
+        if tuple(du_tile.shape) != tuple(du.shape):
+            raise ValueError("du_tile must have du's shape [T, K, 3]")
+        kw = dict(
+            tile=tile.to(torch.float64).contiguous(),
+            du_tile=du_tile.to(device=dev, dtype=torch.float64).contiguous())
+    return _ext().station_beam_gains(
+        elem.to(torch.float64).contiguous(),
+        torch.as_tensor(ne.astype(np.int32)).to(dev),
+        du.to(device=dev, dtype=torch.float64).contiguous(),
+        below.to(device=dev, dtype=torch.uint8).contiguous(),
+        torch.as_tensor(2.0 * math.pi * fq / C_LIGHT).to(dev), **kw)
+
+
 class BaselineLayout:
     """Row-structure descriptor for the solver kernels: rows are
     seg*(T*Nbase) + t*Nbase + b with a fixed pair table. Built once per

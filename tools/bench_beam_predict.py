@@ -12,8 +12,17 @@ text instead of timings. `--cpu-mode2 CALLS` adds wall-clock timings of
 mode 2 on CPU tensors at the same size, the baseline where a revision has
 no working GPU path for it.
 
+`--two-stage` makes every station a two-stage HBA beamformer: `--elements`
+tile centroids and 16 dipoles per tile, tile pointing 0.02 rad off the
+station pointing; it needs a tree that has the two-stage model. The
+work-equivalent single-stage call, on any tree, is `--elements` = tiles + 16
+(the same number of phasors per station). `--gain-channels F` also times
+the station gains of F channels: F single-frequency array_beam_gains calls
+and, where the tree has it, one batched station_beam_gains call.
+
     python tools/bench_beam_predict.py --out result.json [--tree DIR]
-        [--cpu-mode2 CALLS] [--sample sample.pt]
+        [--cpu-mode2 CALLS] [--sample sample.pt] [--modes 1,2,3]
+        [--elements E] [--two-stage] [--gain-channels F]
 """
 import argparse
 import json
@@ -29,7 +38,10 @@ LON, LAT, TMJD0 = 0.1, 0.92, 57000.0
 WARMUP, CALLS = 3, 20
 
 
-def make_inputs(torch):
+TILE_DIPOLES, TILE_OFFSET = 16, (0.02, -0.014)
+
+
+def make_inputs(torch, elements=ELEMS, two_stage=False):
     from sagecal_amd import beams, msdata, sky
     from sagecal_amd.ops.reference import SourcePack
     srcs, clist = sky.make_synthetic_sky(M=DIRS, nsrc_per_cluster=SRCS,
@@ -39,8 +51,14 @@ def make_inputs(torch):
                             pack=None, seed=13, tdelta=TDELTA)
     tile = ms.load_tile(0)
     rng = np.random.default_rng(29)
-    elems = [rng.uniform(-30, 30, (ELEMS, 3)) for _ in range(STATIONS)]
-    cfg = beams.ArrayConfig(elems, LON, LAT, 0.0, DEC0)
+    elems = [rng.uniform(-30, 30, (elements, 3)) for _ in range(STATIONS)]
+    kw = {}
+    if two_stage:
+        kw = dict(bf_type='tile', tile_ra0=TILE_OFFSET[0],
+                  tile_dec0=DEC0 + TILE_OFFSET[1],
+                  tile_enu=rng.uniform(-2.5, 2.5,
+                                       (STATIONS, TILE_DIPOLES, 3)))
+    cfg = beams.ArrayConfig(elems, LON, LAT, 0.0, DEC0, **kw)
     tmjd = TMJD0 + (np.arange(TSLOTS) + 0.5) * TDELTA / 86400.0
     return pack, (tile.u, tile.v, tile.w), ms.bb_tensor(device='cpu'), \
         ms.Nbase, cfg, tmjd
@@ -56,6 +74,15 @@ def main():
     ap.add_argument('--sample', default=None,
                     help='save every 997th output row of each mode here')
     ap.add_argument('--label', default='')
+    ap.add_argument('--modes', default='1,2,3',
+                    help='comma-separated predict modes to time')
+    ap.add_argument('--elements', type=int, default=ELEMS,
+                    help='elements (tile centroids with --two-stage) per '
+                         'station')
+    ap.add_argument('--two-stage', action='store_true',
+                    help='two-stage HBA stations: 16 dipoles per tile')
+    ap.add_argument('--gain-channels', type=int, default=0, metavar='F',
+                    help='also time the station gains of F channels')
     args = ap.parse_args()
     tree = os.path.abspath(args.tree or os.path.join(
         os.path.dirname(os.path.abspath(__file__)), '..'))
@@ -65,13 +92,16 @@ def main():
         sys.exit('bench_beam_predict: no GPU, nothing to measure')
     from sagecal_amd import beams
     dev = torch.device('cuda:0')
-    pack, uvw, bb, Nbase, cfg, tmjd = make_inputs(torch)
+    pack, uvw, bb, Nbase, cfg, tmjd = make_inputs(torch, args.elements,
+                                                  args.two_stage)
     uvw_d = [t.to(dev) for t in uvw]
     bb_d = bb.to(dev)
     res = {'label': args.label, 'tree': os.path.basename(tree),
            'rows': int(uvw[0].shape[0]), 'stations': STATIONS,
            'timeslots': TSLOTS, 'clusters': DIRS, 'sources': DIRS * SRCS,
-           'elements': ELEMS, 'warmup': WARMUP, 'calls': CALLS, 'modes': {}}
+           'elements': args.elements, 'two_stage': args.two_stage,
+           'dipoles_per_tile': TILE_DIPOLES if args.two_stage else 0,
+           'warmup': WARMUP, 'calls': CALLS, 'modes': {}}
     samples = {}
     tag = args.label or res['tree']
 
@@ -80,7 +110,52 @@ def main():
             pack, *rows, FREQ0, FREQ0, FDELTA, TDELTA, DEC0, cfg, tmjd,
             pairs, Nbase, TSLOTS, mode=mode)
 
-    for mode in (1, 2, 3):
+    def timed(fn):
+        """Median-ready list of CALLS device-event timings of fn(), ms."""
+        for _ in range(WARMUP):
+            out = fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(CALLS):
+            e0 = torch.cuda.Event(enable_timing=True)
+            e1 = torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn()
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return ms, out
+
+    def stats(ms):
+        return {'ms_per_call': [round(x, 4) for x in ms],
+                'ms_median': round(float(np.median(ms)), 4),
+                'ms_min': round(min(ms), 4), 'ms_max': round(max(ms), 4)}
+
+    if args.gain_channels > 0:
+        # channel gains alone, geometry prebuilt: F single-frequency calls
+        # against one batched call; any exception ends the job
+        F = args.gain_channels
+        freqs = [FREQ0 + (i - (F - 1) / 2) * FDELTA / F for i in range(F)]
+        geom = beams.beam_geometry(cfg, *beams._pack_radec(pack, DEC0), tmjd)
+        res['gains'] = {'channels': F, 'freqs': freqs}
+        ms, rows = timed(lambda: [beams.array_beam_gains(cfg, geom, f, dev)
+                                  for f in freqs])
+        res['gains']['per_channel_calls'] = stats(ms)
+        print(f'{tag} gains, {F} single-frequency calls: median '
+              f'{np.median(ms):.3f} ms', flush=True)
+        if hasattr(beams, 'station_beam_gains'):
+            ms, batch = timed(lambda: beams.station_beam_gains(
+                cfg, geom, freqs, dev))
+            res['gains']['batched_call'] = stats(ms)
+            res['gains']['batched_vs_per_channel_max_abs'] = float(
+                (batch - torch.stack(rows)).abs().max())
+            print(f'{tag} gains, one batched call: median '
+                  f'{np.median(ms):.3f} ms', flush=True)
+            samples['gains'] = batch[:, ::7, ::13].cpu()
+        else:
+            samples['gains'] = torch.stack(rows)[:, ::7, ::13].cpu()
+
+    for mode in [int(m) for m in args.modes.split(',') if m]:
         try:
             for _ in range(WARMUP):
                 out = predict(mode, uvw_d, bb_d)
