@@ -4,43 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <c10/hip/HIPStream.h>
 
-extern "C" {
-hipError_t launch_predict_coh(const double*, const double*, const double*,
-    const double*, const double*, const double*, const float*,
-    const float*, const float*, const float*, const float*, const float*,
-    const float*, const float*, const float*, const float*, const float*,
-    const float*, const int*, const int*, int, int, double, double,
-    double, const float*, const int*, int, int, int, const float2*, int,
-    float2*, hipStream_t);
-hipError_t launch_array_beam(const double*, const int*, const double*,
-    const unsigned char*, int, int, int, double, float*, hipStream_t);
-hipError_t launch_station_beam(const double*, const int*, const double*,
-    const double*, const double*, const unsigned char*, const double*, int,
-    int, int, int, int, float*, hipStream_t);
-hipError_t launch_shapelet_coh(const double*, const double*, const double*,
-    int, int, const int*, const int*, const int*, const float*, const int*,
-    const float*, const float*, const float*, const float*, const float*,
-    const float*, const float*, const float*, const float*, const float*,
-    const double*, const double*, const double*, const float*, int,
-    const float*, const float*, double, double, double, const float*,
-    const int*, int, int, int, const float2*, int, float2*, hipStream_t);
-hipError_t launch_jtj_accum(const float2*, const float2*, const float2*,
-    const int*, const int*, const int*, const float*, int, int, int, int,
-    int, float2*, float2*, float*, int*, float2*, float2*, float2*, float*,
-    int, int, hipStream_t);
-hipError_t launch_jtj_expand(const float2*, const float2*, const float2*,
-    const int*, const int*, int, int, int, float*, float*, hipStream_t);
-hipError_t launch_model_cost(const float2*, const float2*, const float2*,
-    const int*, const int*, const float*, int, int, int, int, int, float*,
-    float*, hipStream_t);
-hipError_t launch_apply_jones(const float2*, const float2*, const float2*,
-    const int*, const int*, int, int, int, int, int, int, float2*,
-    hipStream_t);
-hipError_t launch_chol_mw(const float*, const float*, const float*, int,
-                          int, float*, float*, int*, hipStream_t);
-hipError_t launch_chol_solve(const float*, const float*, const float*, int,
-    int, float*, float*, int*, hipStream_t);
-}
+#include "launchers.h"
 
 #define CHECK_HIP(x) do { hipError_t e = (x); TORCH_CHECK(e == hipSuccess, \
     "HIP error: ", hipGetErrorString(e)); } while (0)
@@ -55,41 +19,71 @@ static float2* cptr(torch::Tensor& t) {
 static const float2* ccptr(const torch::Tensor& t) {
   return reinterpret_cast<const float2*>(t.data_ptr());
 }
+static const double* dp(const torch::Tensor& t) { return t.data_ptr<double>(); }
+static const float* fp(const torch::Tensor& t) { return t.data_ptr<float>(); }
+static const int* ip(const torch::Tensor& t) { return t.data_ptr<int>(); }
+static RowsUVW rows_uvw(const torch::Tensor& u, const torch::Tensor& v,
+                        const torch::Tensor& w) {
+  RowsUVW rows = {};
+  rows.u = dp(u); rows.v = dp(v); rows.w = dp(w);
+  rows.R = (int)u.size(0);
+  return rows;
+}
 
-// Checks an optional E-Jones buffer [T, K, NE, 2, 2] complex64 against the
-// rows and the beam; returns its pointer (null without one) and sets NE,
-// Ktot and Nsta. The kernels read pairs on every row with it.
-static const float2* ejones_arg(
-    const c10::optional<torch::Tensor>& ejones,
+// The optional station beam of both predict entry points: beam [T, K, N]
+// float32, pairs [Nbase, 2] int32 and ejones [T, K, NE, 2, 2] complex64,
+// checked against the rows of u. The kernels index all three by timeslot,
+// source and station with no bounds of their own, and read pairs on every
+// row with either buffer. Nsta_ej is the station count that ejones goes
+// with (beam brings its own).
+static BeamArgs beam_args(
     const c10::optional<torch::Tensor>& beam,
-    const c10::optional<torch::Tensor>& pairs, const torch::Tensor& u,
-    int64_t Nbase, int64_t Nsta_in, int& NE, int& Ktot, int& Nsta) {
-  NE = 0;
-  if (!ejones.has_value()) return nullptr;
-  const torch::Tensor& e = *ejones;
+    const c10::optional<torch::Tensor>& pairs,
+    const c10::optional<torch::Tensor>& ejones, const torch::Tensor& u,
+    int64_t Nbase, int64_t Nsta_ej) {
+  BeamArgs a = {};
+  if (!beam.has_value() && !ejones.has_value()) return a;
   const int64_t R = u.size(0);
-  TORCH_CHECK(e.is_cuda() && e.device() == u.device() &&
-              e.scalar_type() == torch::kComplexFloat && e.is_contiguous() &&
-              e.dim() == 5 && e.size(3) == 2 && e.size(4) == 2,
-              "ejones must be contiguous [T, K, NE, 2, 2] complex64");
   TORCH_CHECK(pairs.has_value() && Nbase > 0,
-              "ejones needs the station-pair table and Nbase");
+              "beam and ejones need the station-pair table and Nbase");
   TORCH_CHECK(pairs->device() == u.device() &&
               pairs->scalar_type() == torch::kInt && pairs->is_contiguous() &&
               pairs->numel() == 2 * Nbase,
               "pairs must be contiguous [Nbase, 2] int32");
-  TORCH_CHECK(e.size(0) * Nbase == R, "ejones timeslots * Nbase != rows");
-  TORCH_CHECK(Nsta_in > 0, "ejones needs the station count Nsta");
-  TORCH_CHECK(e.size(2) == 1 || e.size(2) == Nsta_in,
-              "ejones must hold 1 or Nsta patterns per source");
-  if (beam.has_value())
-    TORCH_CHECK(beam->size(0) == e.size(0) && beam->size(1) == e.size(1) &&
-                beam->size(2) == Nsta_in,
-                "beam and ejones disagree on [T, K] or Nsta");
-  NE = (int)e.size(2);
-  Ktot = (int)e.size(1);
-  Nsta = (int)Nsta_in;
-  return reinterpret_cast<const float2*>(e.data_ptr());
+  a.pairs = pairs->data_ptr<int>();
+  a.Nbase = (int)Nbase;
+  if (beam.has_value()) {
+    TORCH_CHECK(beam->device() == u.device() &&
+                beam->scalar_type() == torch::kFloat &&
+                beam->is_contiguous() && beam->dim() == 3,
+                "beam must be contiguous [T, K, N] float32");
+    TORCH_CHECK(R <= beam->size(0) * Nbase,
+                "beam has too few timeslots for the rows");
+    a.beam = beam->data_ptr<float>();
+    a.Ktot = (int)beam->size(1);
+    a.Nsta = (int)beam->size(2);
+  }
+  if (ejones.has_value()) {
+    const torch::Tensor& e = *ejones;
+    TORCH_CHECK(e.is_cuda() && e.device() == u.device() &&
+                e.scalar_type() == torch::kComplexFloat &&
+                e.is_contiguous() && e.dim() == 5 && e.size(3) == 2 &&
+                e.size(4) == 2,
+                "ejones must be contiguous [T, K, NE, 2, 2] complex64");
+    TORCH_CHECK(e.size(0) * Nbase == R, "ejones timeslots * Nbase != rows");
+    TORCH_CHECK(Nsta_ej > 0, "ejones needs the station count Nsta");
+    TORCH_CHECK(e.size(2) == 1 || e.size(2) == Nsta_ej,
+                "ejones must hold 1 or Nsta patterns per source");
+    if (beam.has_value())
+      TORCH_CHECK(beam->size(0) == e.size(0) && beam->size(1) == e.size(1) &&
+                  beam->size(2) == Nsta_ej,
+                  "beam and ejones disagree on [T, K] or Nsta");
+    a.ejones = ccptr(e);
+    a.NE = (int)e.size(2);
+    a.Ktot = (int)e.size(1);
+    a.Nsta = (int)Nsta_ej;
+  }
+  return a;
 }
 
 torch::Tensor predict_coh(
@@ -102,36 +96,20 @@ torch::Tensor predict_coh(
     torch::Tensor cluster_off, double freq, double fdelta2, double tdelta,
     c10::optional<torch::Tensor> beam, c10::optional<torch::Tensor> pairs,
     int64_t Nbase, c10::optional<torch::Tensor> ejones, int64_t Nsta_ej) {
-  const int R = u.size(0);
-  const int M = cluster_off.size(0) - 1;
-  auto out = torch::empty({M, R, 4},
+  const BeamArgs bm = beam_args(beam, pairs, ejones, u, Nbase, Nsta_ej);
+  const RowsUVW rows = rows_uvw(u, v, w);
+  SourceArrays src = {};
+  src.ll = dp(ll); src.mm = dp(mm); src.nn1 = dp(nn1);
+  src.sI = fp(sI); src.sQ = fp(sQ); src.sU = fp(sU); src.sV = fp(sV);
+  src.eX = fp(eX); src.eY = fp(eY); src.eP = fp(eP);
+  src.cxi = fp(cxi); src.sxi = fp(sxi); src.cphi = fp(cphi);
+  src.sphi = fp(sphi); src.r1 = fp(r1);
+  src.stype = ip(stype); src.cluster_off = ip(cluster_off);
+  src.M = (int)cluster_off.size(0) - 1;
+  auto out = torch::empty({src.M, rows.R, 4},
       torch::dtype(torch::kComplexFloat).device(u.device()));
-  const float* beam_p = nullptr;
-  const int* pairs_p = nullptr;
-  int Ktot = 0, Nsta = 0;
-  if (beam.has_value()) {
-    TORCH_CHECK(pairs.has_value(), "beam needs the station-pair table");
-    TORCH_CHECK(beam->is_contiguous() && beam->dim() == 3,
-                "beam must be contiguous [T, K, N] float32");
-    beam_p = beam->data_ptr<float>();
-    pairs_p = pairs->data_ptr<int>();
-    Ktot = beam->size(1);
-    Nsta = beam->size(2);
-  }
-  int NE = 0;
-  const float2* ej_p = ejones_arg(ejones, beam, pairs, u, Nbase, Nsta_ej,
-                                  NE, Ktot, Nsta);
-  if (ej_p != nullptr) pairs_p = pairs->data_ptr<int>();
-  CHECK_HIP(launch_predict_coh(
-      u.data_ptr<double>(), v.data_ptr<double>(), w.data_ptr<double>(),
-      ll.data_ptr<double>(), mm.data_ptr<double>(), nn1.data_ptr<double>(),
-      sI.data_ptr<float>(), sQ.data_ptr<float>(), sU.data_ptr<float>(),
-      sV.data_ptr<float>(), eX.data_ptr<float>(), eY.data_ptr<float>(),
-      eP.data_ptr<float>(), cxi.data_ptr<float>(), sxi.data_ptr<float>(),
-      cphi.data_ptr<float>(), sphi.data_ptr<float>(), r1.data_ptr<float>(),
-      stype.data_ptr<int>(), cluster_off.data_ptr<int>(), M, R, freq,
-      fdelta2, tdelta, beam_p, pairs_p, (int)Nbase, Ktot, Nsta, ej_p, NE,
-      cptr(out), cur_stream()));
+  CHECK_HIP(launch_predict_coh(rows, src, {freq, fdelta2, tdelta}, bm,
+                               cptr(out), cur_stream()));
   return out;
 }
 
@@ -187,64 +165,55 @@ void shapelet_coh_add(
   chk(rec, torch::kFloat, rec.numel(), "rec");
   chk(flux, torch::kFloat, 4 * S, "flux");
   chk(r1, torch::kFloat, S, "r1");
-  const float* beam_p = nullptr;
-  const int* pairs_p = nullptr;
-  int Ktot = 0, Nsta = 0;
-  if (beam.has_value()) {
-    TORCH_CHECK(pairs.has_value(), "beam needs the station-pair table");
-    TORCH_CHECK(beam->is_contiguous() && beam->dim() == 3 &&
-                beam->scalar_type() == torch::kFloat &&
-                beam->device() == out.device(),
-                "beam must be contiguous [T, K, N] float32");
-    TORCH_CHECK(Nbase > 0 && R <= beam->size(0) * Nbase,
-                "beam has too few timeslots for the rows");
-    chk(*pairs, torch::kInt, 2 * Nbase, "pairs");
-    beam_p = beam->data_ptr<float>();
-    pairs_p = pairs->data_ptr<int>();
-    Ktot = beam->size(1);
-    Nsta = beam->size(2);
-  }
-  int NE = 0;
-  const float2* ej_p = ejones_arg(ejones, beam, pairs, u, Nbase, Nsta_ej,
-                                  NE, Ktot, Nsta);
-  if (ej_p != nullptr) pairs_p = pairs->data_ptr<int>();
-  CHECK_HIP(launch_shapelet_coh(
-      u.data_ptr<double>(), v.data_ptr<double>(), w.data_ptr<double>(),
-      (int)R, (int)S, src.data_ptr<int>(), cluster.data_ptr<int>(),
-      n0.data_ptr<int>(), beta.data_ptr<float>(), off.data_ptr<int>(),
-      coef.data_ptr<float>(), cxi.data_ptr<float>(), sxi.data_ptr<float>(),
-      cphi.data_ptr<float>(), sphi.data_ptr<float>(),
-      psign.data_ptr<float>(), a.data_ptr<float>(), b.data_ptr<float>(),
-      ceP.data_ptr<float>(), seP.data_ptr<float>(), ll.data_ptr<double>(),
-      mm.data_ptr<double>(), nn1.data_ptr<double>(), rec.data_ptr<float>(),
-      (int)rec.size(1), flux.data_ptr<float>(), r1.data_ptr<float>(), freq,
-      fdelta2, tdelta, beam_p, pairs_p, (int)Nbase, Ktot, Nsta, ej_p, NE,
-      cptr(out), cur_stream()));
+  const BeamArgs bm = beam_args(beam, pairs, ejones, u, Nbase, Nsta_ej);
+  ShapeletTab tab = {};
+  tab.src = ip(src); tab.cluster = ip(cluster); tab.n0 = ip(n0);
+  tab.beta = fp(beta); tab.off = ip(off); tab.coef = fp(coef);
+  tab.cxi = fp(cxi); tab.sxi = fp(sxi); tab.cphi = fp(cphi);
+  tab.sphi = fp(sphi); tab.psign = fp(psign); tab.a = fp(a); tab.b = fp(b);
+  tab.ceP = fp(ceP); tab.seP = fp(seP);
+  tab.ll = dp(ll); tab.mm = dp(mm); tab.nn1 = dp(nn1);
+  tab.rec = fp(rec); tab.S = (int)S; tab.nmax = (int)rec.size(1);
+  tab.flux = fp(flux); tab.r1 = fp(r1);
+  CHECK_HIP(launch_shapelet_coh(rows_uvw(u, v, w), tab,
+                                {freq, fdelta2, tdelta}, bm, cptr(out),
+                                cur_stream()));
 }
 
-// gain[t,k,n] of k_array_beam: elem [N, Emax, 3] float64, nelem [N] int32
-// (the caller has checked 1 <= nelem <= Emax on the host), du [T, K, 3]
-// float64, below [T, K] uint8, kf = 2 pi f / c. Returns [T, K, N] float32.
-torch::Tensor array_beam_gains(
-    torch::Tensor elem, torch::Tensor nelem, torch::Tensor du,
-    torch::Tensor below, double kf) {
+// The four tensors both beam-gain entry points share: elem [N, Emax, 3]
+// float64 on the device, nelem [N] int32 (the caller has checked
+// 1 <= nelem <= Emax on the host), du [T, K, 3] float64, below [T, K] uint8.
+static void check_beam_geometry(
+    const torch::Tensor& elem, const torch::Tensor& nelem,
+    const torch::Tensor& du, const torch::Tensor& below) {
   TORCH_CHECK(elem.is_cuda() && elem.scalar_type() == torch::kDouble &&
               elem.is_contiguous() && elem.dim() == 3 && elem.size(2) == 3 &&
               elem.size(1) > 0, "elem must be contiguous [N, Emax, 3] float64");
-  const int64_t N = elem.size(0), Emax = elem.size(1);
   TORCH_CHECK(nelem.device() == elem.device() &&
               nelem.scalar_type() == torch::kInt && nelem.is_contiguous() &&
-              nelem.numel() == N, "nelem must be contiguous [N] int32");
+              nelem.numel() == elem.size(0),
+              "nelem must be contiguous [N] int32");
   TORCH_CHECK(du.device() == elem.device() &&
               du.scalar_type() == torch::kDouble && du.is_contiguous() &&
               du.dim() == 3 && du.size(2) == 3,
               "du must be contiguous [T, K, 3] float64");
-  const int64_t T = du.size(0), K = du.size(1);
   TORCH_CHECK(below.device() == elem.device() &&
               below.scalar_type() == torch::kByte && below.is_contiguous() &&
-              below.dim() == 2 && below.size(0) == T && below.size(1) == K,
+              below.dim() == 2 && below.size(0) == du.size(0) &&
+              below.size(1) == du.size(1),
               "below must be contiguous [T, K] uint8");
-  TORCH_CHECK(T * K < (int64_t(1) << 31), "too many (timeslot, source) pairs");
+  TORCH_CHECK(du.size(0) * du.size(1) < (int64_t(1) << 31),
+              "too many (timeslot, source) pairs");
+}
+
+// gain[t,k,n] of k_array_beam for the tensors of check_beam_geometry and
+// kf = 2 pi f / c. Returns [T, K, N] float32.
+torch::Tensor array_beam_gains(
+    torch::Tensor elem, torch::Tensor nelem, torch::Tensor du,
+    torch::Tensor below, double kf) {
+  check_beam_geometry(elem, nelem, du, below);
+  const int64_t N = elem.size(0), Emax = elem.size(1);
+  const int64_t T = du.size(0), K = du.size(1);
   auto gain = torch::empty({T, K, N},
       torch::dtype(torch::kFloat).device(elem.device()));
   CHECK_HIP(launch_array_beam(elem.data_ptr<double>(), nelem.data_ptr<int>(),
@@ -262,27 +231,13 @@ torch::Tensor station_beam_gains(
     torch::Tensor elem, torch::Tensor nelem, torch::Tensor du,
     torch::Tensor below, torch::Tensor kf,
     c10::optional<torch::Tensor> tile, c10::optional<torch::Tensor> du_tile) {
-  TORCH_CHECK(elem.is_cuda() && elem.scalar_type() == torch::kDouble &&
-              elem.is_contiguous() && elem.dim() == 3 && elem.size(2) == 3 &&
-              elem.size(1) > 0, "elem must be contiguous [N, Emax, 3] float64");
+  check_beam_geometry(elem, nelem, du, below);
   const int64_t N = elem.size(0), Emax = elem.size(1);
-  TORCH_CHECK(nelem.device() == elem.device() &&
-              nelem.scalar_type() == torch::kInt && nelem.is_contiguous() &&
-              nelem.numel() == N, "nelem must be contiguous [N] int32");
-  TORCH_CHECK(du.device() == elem.device() &&
-              du.scalar_type() == torch::kDouble && du.is_contiguous() &&
-              du.dim() == 3 && du.size(2) == 3,
-              "du must be contiguous [T, K, 3] float64");
   const int64_t T = du.size(0), K = du.size(1);
-  TORCH_CHECK(below.device() == elem.device() &&
-              below.scalar_type() == torch::kByte && below.is_contiguous() &&
-              below.dim() == 2 && below.size(0) == T && below.size(1) == K,
-              "below must be contiguous [T, K] uint8");
   TORCH_CHECK(kf.device() == elem.device() &&
               kf.scalar_type() == torch::kDouble && kf.is_contiguous() &&
               kf.dim() == 1, "kf must be contiguous [F] float64");
   const int64_t F = kf.size(0);
-  TORCH_CHECK(T * K < (int64_t(1) << 31), "too many (timeslot, source) pairs");
   TORCH_CHECK(tile.has_value() == du_tile.has_value(),
               "tile and du_tile come together");
   const double* tile_p = nullptr;

@@ -1,0 +1,115 @@
+// The interface between launchers.hip (hipcc) and bindings.cpp (host
+// compiler): every launch_* prototype and the argument structs of the two
+// predict launchers. Both sides include this file, so a signature that
+// changes on one side alone does not compile.
+//
+// The structs exist at the binding / launcher / kernel boundary only. A
+// kernel takes them by value and unpacks each exactly once into the
+// __restrict__ parameter list of its __device__ __forceinline__ body
+// (predict.hip says why); nothing in a body reads a struct member.
+#pragma once
+#include <hip/hip_runtime.h>
+
+// Baseline rows r = t*Nbase + b, uvw in seconds.
+struct RowsUVW {
+  const double *u, *v, *w;  // [R]
+  int R;
+};
+
+// Per-source arrays of k_predict_coh (hip_host.GPUPack), K sources in M
+// clusters; fluxes at the channel, shapelet sources zeroed.
+struct SourceArrays {
+  const double *ll, *mm, *nn1;
+  const float *sI, *sQ, *sU, *sV;
+  const float *eX, *eY, *eP;
+  const float *cxi, *sxi, *cphi, *sphi;
+  const float* r1;          // time-smear source-distance term
+  const int* stype;
+  const int* cluster_off;   // [M + 1]
+  int M;
+};
+
+// Shapelet mode table of k_shapelet_coh, S entries; the pointers in
+// hip_host.ShapeletTable.FIELDS order, then what changes per call.
+struct ShapeletTab {
+  const int *src, *cluster, *n0;
+  const float* beta;
+  const int* off;           // [S + 1]
+  const float* coef;
+  const float *cxi, *sxi, *cphi, *sphi, *psign, *a, *b, *ceP, *seP;
+  const double *ll, *mm, *nn1;
+  const float* rec;         // [2, nmax]
+  int S, nmax;
+  const float* flux;        // [4, S] I,Q,U,V at the channel
+  const float* r1;          // [S]
+};
+
+struct Channel {
+  double freq;
+  double fdelta2;           // channel halfwidth [Hz]
+  double tdelta;
+};
+
+// Station beam of both predict kernels. beam null: no scalar gain; ejones
+// null: the kernels without E-Jones run. pairs, Nbase and Ktot are read
+// with either; Nsta strides beam, NE (1 or Nsta) strides ejones.
+struct BeamArgs {
+  const float* beam;        // [T, Ktot, Nsta] or null
+  const int* pairs;         // [Nbase, 2]
+  int Nbase, Ktot, Nsta;
+  const float2* ejones;     // [T, Ktot, NE, 2, 2] or null
+  int NE;
+};
+
+extern "C" {
+
+// out [M, R, 4]: written by launch_predict_coh, added into by
+// launch_shapelet_coh. hipErrorInvalidValue: ejones without pairs or
+// Nbase, or NE neither 1 nor Nsta.
+hipError_t launch_predict_coh(RowsUVW rows, SourceArrays src, Channel ch,
+                              BeamArgs bm, float2* out, hipStream_t stream);
+hipError_t launch_shapelet_coh(RowsUVW rows, ShapeletTab tab, Channel ch,
+                               BeamArgs bm, float2* out, hipStream_t stream);
+
+hipError_t launch_array_beam(
+    const double* elem, const int* nelem, const double* du,
+    const unsigned char* below, int N, int Emax, int TK, double kf,
+    float* gain, hipStream_t stream);
+// tile and du_tile come together or not at all (single stage); D counts
+// the dipoles of a tile and is ignored without them
+hipError_t launch_station_beam(
+    const double* elem, const int* nelem, const double* tile,
+    const double* du, const double* du_tile, const unsigned char* below,
+    const double* kfs, int N, int Emax, int D, int TK, int F, float* gain,
+    hipStream_t stream);
+
+hipError_t launch_jtj_accum(
+    const float2* x, const float2* coh, const float2* J, const int* pairs,
+    const int* chunk_tab, const int* pidx, const float* wts, int Nbase,
+    int T, int N, int nseg, int Mt, float2* PD, float2* Pg, float* Pc,
+    int* present, float2* D, float2* g, float2* Cx, float* cost, int npair,
+    int grad_only, hipStream_t stream);
+hipError_t launch_jtj_expand(
+    const float2* D, const float2* g, const float2* Cx, const int* pairs,
+    const int* pidx, int N, int npair, int Mt, float* JtJ, float* Jtr,
+    hipStream_t stream);
+hipError_t launch_model_cost(
+    const float2* x, const float2* coh, const float2* J, const int* pairs,
+    const int* chunk_tab, const float* wts, int Nbase, int T, int N,
+    int nseg, int Mt, float* e2, float* cost, hipStream_t stream);
+hipError_t launch_apply_jones(
+    const float2* x, const float2* cohs, const float2* J, const int* pairs,
+    const int* chunk_tab, int Nbase, int T, int N, int nseg, int M, int sub,
+    float2* out, hipStream_t stream);
+
+// dp = (JtJ + mu I)^-1 Jtr, one workgroup per problem (chol_solve) or the
+// multi-workgroup kernel sequence (chol_mw); same contract, n a multiple of
+// the block size, Lbuf 2*n*n floats per problem
+hipError_t launch_chol_solve(
+    const float* JtJ, const float* Jtr, const float* mu, int n, int batch,
+    float* Lbuf, float* dp, int* info, hipStream_t stream);
+hipError_t launch_chol_mw(
+    const float* JtJ, const float* Jtr, const float* mu, int n, int batch,
+    float* Lbuf, float* dp, int* info, hipStream_t stream);
+
+}  // extern "C"

@@ -1,70 +1,42 @@
 // Kernel launch wrappers + kernels in ONE translation unit (no -fgpu-rdc
 // cross-TU device linking needed).
 #include "common.h"
+#include "launchers.h"
 #include "predict.hip"
 #include "jtj.hip"
 #include "cholesky.hip"
 
-extern "C" {
-
-hipError_t launch_predict_coh(
-    const double* u, const double* v, const double* w, const double* ll,
-    const double* mm, const double* nn1, const float* sI, const float* sQ,
-    const float* sU, const float* sV, const float* eX, const float* eY,
-    const float* eP, const float* cxi, const float* sxi, const float* cphi,
-    const float* sphi, const float* r1, const int* stype,
-    const int* cluster_off, int M, int R, double freq, double fdelta2,
-    double tdelta, const float* beam, const int* pairs, int Nbase,
-    int Ktot, int Nsta, const float2* ejones, int NE, float2* out,
-    hipStream_t stream) {
+// One thread per row in blocks of 128: the plain kernel, or with
+// bm.ejones the _ej one, which reads pairs on every row. The two take the
+// same arguments.
+template <typename Args>
+static hipError_t launch_rows(
+    void (*plain)(RowsUVW, Args, Channel, BeamArgs, float2*),
+    void (*ej)(RowsUVW, Args, Channel, BeamArgs, float2*), RowsUVW rows,
+    Args args, Channel ch, BeamArgs bm, float2* out, hipStream_t stream) {
+  const bool with_ej = bm.ejones != nullptr;
+  if (with_ej && (bm.pairs == nullptr || bm.Nbase <= 0 ||
+                  (bm.NE != 1 && bm.NE != bm.Nsta)))
+    return hipErrorInvalidValue;
   const int tb = 128;
-  const int nb = (R + tb - 1) / tb;
-  if (ejones != nullptr) {
-    // E-Jones variant; it reads pairs on every row
-    if (pairs == nullptr || Nbase <= 0 || (NE != 1 && NE != Nsta))
-      return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_predict_coh_ej, dim3(nb), dim3(tb), 0, stream,
-        u, v, w, ll, mm, nn1, sI, sQ, sU, sV, eX, eY, eP, cxi, sxi, cphi,
-        sphi, r1, stype, cluster_off, M, R, freq, fdelta2, tdelta,
-        beam, pairs, Nbase, Ktot, Nsta, ejones, NE, out);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(k_predict_coh, dim3(nb), dim3(tb), 0, stream,
-      u, v, w, ll, mm, nn1, sI, sQ, sU, sV, eX, eY, eP, cxi, sxi, cphi,
-      sphi, r1, stype, cluster_off, M, R, freq, fdelta2, tdelta,
-      beam, pairs, Nbase, Ktot, Nsta, out);
+  hipLaunchKernelGGL(with_ej ? ej : plain, dim3((rows.R + tb - 1) / tb),
+                     dim3(tb), 0, stream, rows, args, ch, bm, out);
   return hipGetLastError();
 }
 
-hipError_t launch_shapelet_coh(
-    const double* u, const double* v, const double* w, int R, int S,
-    const int* src, const int* cluster, const int* n0, const float* beta,
-    const int* off, const float* coef, const float* cxi, const float* sxi,
-    const float* cphi, const float* sphi, const float* psign,
-    const float* a, const float* b, const float* ceP, const float* seP,
-    const double* ll, const double* mm, const double* nn1,
-    const float* rec, int nmax, const float* flux, const float* r1,
-    double freq, double fdelta2, double tdelta, const float* beam,
-    const int* pairs, int Nbase, int Ktot, int Nsta, const float2* ejones,
-    int NE, float2* out, hipStream_t stream) {
-  if (S <= 0 || R <= 0) return hipSuccess;
-  const int tb = 128;
-  const int nb = (R + tb - 1) / tb;
-  if (ejones != nullptr) {
-    if (pairs == nullptr || Nbase <= 0 || (NE != 1 && NE != Nsta))
-      return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_shapelet_coh_ej, dim3(nb), dim3(tb), 0, stream,
-        u, v, w, R, S, src, cluster, n0, beta, off, coef, cxi, sxi, cphi,
-        sphi, psign, a, b, ceP, seP, ll, mm, nn1, rec, nmax, flux, r1,
-        freq, fdelta2, tdelta, beam, pairs, Nbase, Ktot, Nsta, ejones, NE,
-        out);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(k_shapelet_coh, dim3(nb), dim3(tb), 0, stream,
-      u, v, w, R, S, src, cluster, n0, beta, off, coef, cxi, sxi, cphi,
-      sphi, psign, a, b, ceP, seP, ll, mm, nn1, rec, nmax, flux, r1,
-      freq, fdelta2, tdelta, beam, pairs, Nbase, Ktot, Nsta, out);
-  return hipGetLastError();
+extern "C" {
+
+hipError_t launch_predict_coh(RowsUVW rows, SourceArrays src, Channel ch,
+                              BeamArgs bm, float2* out, hipStream_t stream) {
+  return launch_rows(k_predict_coh, k_predict_coh_ej, rows, src, ch, bm, out,
+                     stream);
+}
+
+hipError_t launch_shapelet_coh(RowsUVW rows, ShapeletTab tab, Channel ch,
+                               BeamArgs bm, float2* out, hipStream_t stream) {
+  if (tab.S <= 0 || rows.R <= 0) return hipSuccess;
+  return launch_rows(k_shapelet_coh, k_shapelet_coh_ej, rows, tab, ch, bm,
+                     out, stream);
 }
 
 hipError_t launch_array_beam(

@@ -26,13 +26,36 @@
 // accumulators are the four coherency entries instead of four Stokes sums.
 // They are compile-time variants (template parameter EJ) of one body: the
 // kernels without E-Jones carry none of this code and no branch for it.
+//
+// Arguments. The kernels take the structs of launchers.h by value (RowsUVW,
+// SourceArrays or ShapeletTab, Channel, BeamArgs), the same ones the
+// bindings fill by field name. Each kernel family has one unpack function
+// (predict_coh_kernel, shapelet_coh_kernel) that forwards the fields to the
+// __restrict__ parameter list of a __device__ __forceinline__ body, and
+// bodies and helpers work on those parameters and on values only, never on
+// a struct member. __restrict__ carries noalias on function parameters
+// alone: through a struct member, or a local __restrict__ copy of one, the
+// compiler cannot prove that the out[] read-modify-write of k_shapelet_coh
+// leaves the table alone, and turns the block-uniform table reads from
+// scalar into per-lane vector loads. hipcc -O3 for gfx950, k_shapelet_coh
+// (the _ej kernel moves the same way, 748/69/48/14 -> 760/73/18/42):
+//                                       instrs  VGPR  s_load  global_load
+//   positional arguments                   632    50      47           10
+//   body reads struct members              642    52      15           38
+//   struct fields forwarded to the body    628    50      43           10
+// (this file as it stands: 629/50/43/10 and 738/69/46/14). Two more things
+// cost VGPRs in the _ej kernels, so the helpers avoid them: a second local
+// array between the sums and the store (put_coherency hands each entry to
+// a callback), and fluxes read before the beam gains (add_source takes a
+// flux(i) callable).
 #include "common.h"
+#include "launchers.h"
 
 #define SRC_TILE 64
 
 struct SrcTile {
   double ll[SRC_TILE], mm[SRC_TILE], nn1[SRC_TILE];
-  float sI[SRC_TILE], sQ[SRC_TILE], sU[SRC_TILE], sV[SRC_TILE];
+  float flux[4][SRC_TILE];  // Stokes I,Q,U,V
   float eX[SRC_TILE], eY[SRC_TILE], eP[SRC_TILE];
   float cxi[SRC_TILE], sxi[SRC_TILE], cphi[SRC_TILE], sphi[SRC_TILE];
   float r1[SRC_TILE];  // time-smear source-distance term (precomputed host)
@@ -88,48 +111,99 @@ __device__ __forceinline__ void ej_accumulate(cf phc, float fI, float fQ,
   for (int i = 0; i < 4; ++i) acc[i] = cadd(acc[i], S[i]);
 }
 
-#define PREDICT_COH_PARAMS                                                  \
-    const double* __restrict__ u, const double* __restrict__ v,             \
-    const double* __restrict__ w, const double* __restrict__ ll,            \
-    const double* __restrict__ mm, const double* __restrict__ nn1,          \
-    const float* __restrict__ sI, const float* __restrict__ sQ,             \
-    const float* __restrict__ sU, const float* __restrict__ sV,             \
-    const float* __restrict__ eX, const float* __restrict__ eY,             \
-    const float* __restrict__ eP, const float* __restrict__ cxi,            \
-    const float* __restrict__ sxi, const float* __restrict__ cphi,          \
-    const float* __restrict__ sphi, const float* __restrict__ r1t,          \
-    const int* __restrict__ stype, const int* __restrict__ cluster_off,     \
-    int M, int R, double freq,                                              \
-    double fdelta2,                   /* channel halfwidth [Hz] */          \
-    double tdelta,                                                          \
-    const float* __restrict__ beam,   /* [T, K, N] or null */               \
-    const int* __restrict__ pairs,    /* [Nbase, 2] (with beam or EJ) */    \
-    int Nbase, int Ktot, int Nsta
-#define PREDICT_COH_ARGS                                                    \
-    u, v, w, ll, mm, nn1, sI, sQ, sU, sV, eX, eY, eP, cxi, sxi, cphi, sphi, \
-    r1t, stype, cluster_off, M, R, freq, fdelta2, tdelta, beam, pairs,      \
-    Nbase, Ktot, Nsta
+// Beam indexing state of one row: its two stations, their E-Jones patterns
+// and the offset of its timeslot in units of sources.
+struct BeamRow {
+  int sta1, sta2;    // stations of the baseline (index into beam[t,k,:])
+  int pat1, pat2;    // E-Jones pattern of each: its own, or 0 when NE == 1
+  size_t toff;       // t * Ktot
+};
+
+// `on`: the row is live and there is a beam or E-Jones; all zero otherwise,
+// and pairs is not read.
+__device__ __forceinline__ BeamRow beam_row(bool on, int r,
+                                            const int* __restrict__ pairs,
+                                            int Nbase, int Ktot, int NE) {
+  BeamRow br = {0, 0, 0, 0, 0};
+  if (on) {
+    const int t = r / Nbase, bl = r - t * Nbase;
+    br.sta1 = pairs[2 * bl];
+    br.sta2 = pairs[2 * bl + 1];
+    br.toff = (size_t)t * Ktot;
+  }
+  br.pat1 = NE == 1 ? 0 : br.sta1;
+  br.pat2 = NE == 1 ? 0 : br.sta2;
+  return br;
+}
+
+// Adds source `src` (index along K) with phase term phc to the sums of one
+// row, scaled by the beam gains of the row's stations when beam is
+// non-null. flux(i), i = 0..3, reads its Stokes I,Q,U,V; it is called after
+// the beam lookup, the order the kernels' register budget was tuned with.
+// The sums a[4] are the Stokes sums I,Q,U,V of phc*flux, or with EJ the
+// four coherency entries after the sandwich.
+template <bool EJ, typename Flux>
+__device__ __forceinline__ void add_source(
+    cf phc, Flux flux, int src, const BeamRow& br,
+    const float* __restrict__ beam, int Nsta,
+    const float2* __restrict__ ejones, int NE, cf* a) {
+  if constexpr (EJ) {
+    const size_t tk = br.toff + (size_t)src;
+    float g = 1.0f;
+    if (beam != nullptr) {
+      const float* bg = beam + tk * (size_t)Nsta;
+      g = bg[br.sta1] * bg[br.sta2];
+    }
+    const cf* ej = ejones + tk * (size_t)NE * 4;
+    ej_accumulate(phc, flux(0), flux(1), flux(2), flux(3), g,
+                  ej + 4 * br.pat1, ej + 4 * br.pat2, a);
+  } else {
+    if (beam != nullptr) {
+      const float* bg = beam + (br.toff + (size_t)src) * (size_t)Nsta;
+      phc = cscale(phc, bg[br.sta1] * bg[br.sta2]);
+    }
+    for (int i = 0; i < 4; ++i) a[i] = cadd(a[i], cscale(phc, flux(i)));
+  }
+}
+
+// Hands put(i, c) the four coherency entries of the sums a[4] of
+// add_source: with EJ the sums themselves, else Stokes -> coherency
+// [[I+Q, U+jV],[U-jV, I-Q]] (predict.c:228-235). k_predict_coh stores them,
+// k_shapelet_coh adds them.
+template <bool EJ, typename Put>
+__device__ __forceinline__ void put_coherency(const cf* a, Put put) {
+  if constexpr (EJ) {
+    for (int i = 0; i < 4; ++i) put(i, a[i]);
+  } else {
+    put(0, cadd(a[0], a[1]));
+    put(1, {a[2].x - a[3].y, a[2].y + a[3].x});
+    put(2, {a[2].x + a[3].y, a[2].y - a[3].x});
+    put(3, csub(a[0], a[1]));
+  }
+}
 
 template <bool EJ>
 __device__ __forceinline__ void predict_coh_body(
-    PREDICT_COH_PARAMS,
-    const float2* __restrict__ ejones,  // [T, K, NE, 2, 2] (EJ)
-    int NE,
-    float2* __restrict__ out) {
+    const double* __restrict__ u, const double* __restrict__ v,
+    const double* __restrict__ w, int R,
+    const double* __restrict__ ll, const double* __restrict__ mm,
+    const double* __restrict__ nn1,
+    const float* __restrict__ sI, const float* __restrict__ sQ,
+    const float* __restrict__ sU, const float* __restrict__ sV,
+    const float* __restrict__ eX, const float* __restrict__ eY,
+    const float* __restrict__ eP, const float* __restrict__ cxi,
+    const float* __restrict__ sxi, const float* __restrict__ cphi,
+    const float* __restrict__ sphi, const float* __restrict__ r1t,
+    const int* __restrict__ stype, const int* __restrict__ cluster_off,
+    int M, double freq, double fdelta2, double tdelta,
+    const float* __restrict__ beam, const int* __restrict__ pairs,
+    int Nbase, int Ktot, int Nsta, const float2* __restrict__ ejones,
+    int NE, float2* __restrict__ out) {
   __shared__ SrcTile tile;
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = r < R;
-  // beam indexing state (only touched when beam != null, or with EJ)
-  int b_sta1 = 0, b_sta2 = 0;
-  size_t b_toff = 0;
-  if ((EJ || beam != nullptr) && live) {
-    const int t = r / Nbase, bl = r - t * Nbase;
-    b_sta1 = pairs[2 * bl];
-    b_sta2 = pairs[2 * bl + 1];
-    b_toff = (size_t)t * Ktot;
-  }
-  // E-Jones pattern of each station: its own, or pattern 0 when NE == 1
-  const int e_sta1 = NE == 1 ? 0 : b_sta1, e_sta2 = NE == 1 ? 0 : b_sta2;
+  const BeamRow br = beam_row((EJ || beam != nullptr) && live, r, pairs,
+                              Nbase, Ktot, NE);
   double ur = 0, vr = 0, wr = 0;
   float blf = 0.f;
   if (live) {
@@ -142,9 +216,8 @@ __device__ __forceinline__ void predict_coh_body(
 
   for (int ci = 0; ci < M; ++ci) {
     const int s0 = cluster_off[ci], s1 = cluster_off[ci + 1];
-    // accumulators: IIl/QQl/UUl/VVl sums as complex
-    cf aI = {0.f, 0.f}, aQ = {0.f, 0.f}, aU = {0.f, 0.f}, aV = {0.f, 0.f};
-    // with EJ: the four coherency entries themselves
+    // sums of add_source: IIl/QQl/UUl/VVl as complex, or with EJ the four
+    // coherency entries themselves
     cf acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
     for (int base = s0; base < s1; base += SRC_TILE) {
       const int nt = min(SRC_TILE, s1 - base);
@@ -152,8 +225,8 @@ __device__ __forceinline__ void predict_coh_body(
       for (int k = threadIdx.x; k < nt; k += blockDim.x) {
         const int g = base + k;
         tile.ll[k] = ll[g];   tile.mm[k] = mm[g];   tile.nn1[k] = nn1[g];
-        tile.sI[k] = sI[g];   tile.sQ[k] = sQ[g];
-        tile.sU[k] = sU[g];   tile.sV[k] = sV[g];
+        tile.flux[0][k] = sI[g];   tile.flux[1][k] = sQ[g];
+        tile.flux[2][k] = sU[g];   tile.flux[3][k] = sV[g];
         tile.eX[k] = eX[g];   tile.eY[k] = eY[g];   tile.eP[k] = eP[g];
         tile.cxi[k] = cxi[g]; tile.sxi[k] = sxi[g];
         tile.cphi[k] = cphi[g]; tile.sphi[k] = sphi[g];
@@ -191,55 +264,43 @@ __device__ __forceinline__ void predict_coh_body(
           }
           // st==4 (shapelet): fluxes are zero here, k_shapelet_coh adds them
         }
-        if constexpr (EJ) {
-          const size_t tk = b_toff + (size_t)(base + k);
-          float g = 1.0f;
-          if (beam != nullptr) {
-            const float* bg = beam + tk * (size_t)Nsta;
-            g = bg[b_sta1] * bg[b_sta2];
-          }
-          const cf* ej = ejones + tk * (size_t)NE * 4;
-          ej_accumulate(phc, tile.sI[k], tile.sQ[k], tile.sU[k], tile.sV[k],
-                        g, ej + 4 * e_sta1, ej + 4 * e_sta2, acc);
-          continue;
-        }
-        if (beam != nullptr) {
-          const float* bg = beam +
-              (b_toff + (size_t)(base + k)) * (size_t)Nsta;
-          phc = cscale(phc, bg[b_sta1] * bg[b_sta2]);
-        }
-        aI = cadd(aI, cscale(phc, tile.sI[k]));
-        aQ = cadd(aQ, cscale(phc, tile.sQ[k]));
-        aU = cadd(aU, cscale(phc, tile.sU[k]));
-        aV = cadd(aV, cscale(phc, tile.sV[k]));
+        add_source<EJ>(phc, [&](int i) { return tile.flux[i][k]; }, base + k,
+                       br, beam, Nsta, ejones, NE, acc);
       }
     }
     if (live) {
-      // Stokes -> coherency [[I+Q, U+jV],[U-jV, I-Q]] (predict.c:228-235)
       float2* o = out + ((size_t)ci * R + r) * 4;
-      if constexpr (EJ) {
-        o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2]; o[3] = acc[3];
-      } else {
-        o[0] = cadd(aI, aQ);
-        o[1] = {aU.x - aV.y, aU.y + aV.x};
-        o[2] = {aU.x + aV.y, aU.y - aV.x};
-        o[3] = csub(aI, aQ);
-      }
+      put_coherency<EJ>(acc, [&](int i, cf c) { o[i] = c; });
     }
     __syncthreads();
   }
 }
 
+// The one place that unpacks the argument structs of this kernel family.
+// Without EJ the body gets no E-Jones, whatever bm holds.
+template <bool EJ>
+__device__ __forceinline__ void predict_coh_kernel(
+    const RowsUVW& rows, const SourceArrays& s, const Channel& ch,
+    const BeamArgs& bm, float2* __restrict__ out) {
+  predict_coh_body<EJ>(
+      rows.u, rows.v, rows.w, rows.R, s.ll, s.mm, s.nn1, s.sI, s.sQ, s.sU,
+      s.sV, s.eX, s.eY, s.eP, s.cxi, s.sxi, s.cphi, s.sphi, s.r1, s.stype,
+      s.cluster_off, s.M, ch.freq, ch.fdelta2, ch.tdelta, bm.beam, bm.pairs,
+      bm.Nbase, bm.Ktot, bm.Nsta, EJ ? bm.ejones : nullptr, EJ ? bm.NE : 0,
+      out);
+}
+
 extern "C" __global__ void __launch_bounds__(128)
-k_predict_coh(PREDICT_COH_PARAMS, float2* __restrict__ out) {
-  predict_coh_body<false>(PREDICT_COH_ARGS, nullptr, 0, out);
+k_predict_coh(RowsUVW rows, SourceArrays src, Channel ch, BeamArgs bm,
+              float2* __restrict__ out) {
+  predict_coh_kernel<false>(rows, src, ch, bm, out);
 }
 
 // E-Jones variant: pairs, Nbase and Ktot are required; beam may be null.
 extern "C" __global__ void __launch_bounds__(128)
-k_predict_coh_ej(PREDICT_COH_PARAMS, const float2* __restrict__ ejones,
-                 int NE, float2* __restrict__ out) {
-  predict_coh_body<true>(PREDICT_COH_ARGS, ejones, NE, out);
+k_predict_coh_ej(RowsUVW rows, SourceArrays src, Channel ch, BeamArgs bm,
+                 float2* __restrict__ out) {
+  predict_coh_kernel<true>(rows, src, ch, bm, out);
 }
 
 // Shapelet sources, added into the coherencies k_predict_coh has written
@@ -260,47 +321,29 @@ k_predict_coh_ej(PREDICT_COH_PARAMS, const float2* __restrict__ ejones,
 // and 2 pi a b are folded into coef on the host. phi_n is the normalised
 // Hermite function, phi_0 = e^{-x^2/2}/sqrt(2), phi_n = x sqrt(2/n)
 // phi_{n-1} - sqrt((n-1)/n) phi_{n-2}; rec holds the two constants per n.
-#define SHAPELET_COH_PARAMS                                                 \
-    const double* __restrict__ u, const double* __restrict__ v,             \
-    const double* __restrict__ w, int R, int S,                             \
-    const int* __restrict__ src, const int* __restrict__ cluster,           \
-    const int* __restrict__ n0t, const float* __restrict__ betat,           \
-    const int* __restrict__ off, const float* __restrict__ coef,            \
-    const float* __restrict__ cxi, const float* __restrict__ sxi,           \
-    const float* __restrict__ cphi, const float* __restrict__ sphi,         \
-    const float* __restrict__ psign, const float* __restrict__ at,          \
-    const float* __restrict__ bt, const float* __restrict__ ceP,            \
-    const float* __restrict__ seP, const double* __restrict__ ll,           \
-    const double* __restrict__ mm, const double* __restrict__ nn1,          \
-    const float* __restrict__ rec, int nmax,  /* [2, nmax] */               \
-    const float* __restrict__ flux,           /* [4, S] I,Q,U,V */          \
-    const float* __restrict__ r1t,            /* [S] */                     \
-    double freq, double fdelta2, double tdelta,                             \
-    const float* __restrict__ beam,   /* [T, K, N] or null */               \
-    const int* __restrict__ pairs,    /* [Nbase, 2] (with beam) */          \
-    int Nbase, int Ktot, int Nsta
-#define SHAPELET_COH_ARGS                                                   \
-    u, v, w, R, S, src, cluster, n0t, betat, off, coef, cxi, sxi, cphi,     \
-    sphi, psign, at, bt, ceP, seP, ll, mm, nn1, rec, nmax, flux, r1t, freq, \
-    fdelta2, tdelta, beam, pairs, Nbase, Ktot, Nsta
-
 template <bool EJ>
 __device__ __forceinline__ void shapelet_coh_body(
-    SHAPELET_COH_PARAMS,
-    const float2* __restrict__ ejones,  // [T, K, NE, 2, 2] (EJ)
-    int NE,
-    float2* out) {                      // [M, R, 4], added into
+    const double* __restrict__ u, const double* __restrict__ v,
+    const double* __restrict__ w, int R,
+    const int* __restrict__ src, const int* __restrict__ cluster,
+    const int* __restrict__ n0t, const float* __restrict__ betat,
+    const int* __restrict__ off, const float* __restrict__ coef,
+    const float* __restrict__ cxi, const float* __restrict__ sxi,
+    const float* __restrict__ cphi, const float* __restrict__ sphi,
+    const float* __restrict__ psign, const float* __restrict__ at,
+    const float* __restrict__ bt, const float* __restrict__ ceP,
+    const float* __restrict__ seP, const double* __restrict__ ll,
+    const double* __restrict__ mm, const double* __restrict__ nn1,
+    const float* __restrict__ rec, int S, int nmax,
+    const float* __restrict__ flux, const float* __restrict__ r1t,
+    double freq, double fdelta2, double tdelta,
+    const float* __restrict__ beam, const int* __restrict__ pairs,
+    int Nbase, int Ktot, int Nsta, const float2* __restrict__ ejones,
+    int NE, float2* out) {              // [M, R, 4], added into
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
-  int b_sta1 = 0, b_sta2 = 0;
-  size_t b_toff = 0;
-  if (EJ || beam != nullptr) {
-    const int t = r / Nbase, bl = r - t * Nbase;
-    b_sta1 = pairs[2 * bl];
-    b_sta2 = pairs[2 * bl + 1];
-    b_toff = (size_t)t * Ktot;
-  }
-  const int e_sta1 = NE == 1 ? 0 : b_sta1, e_sta2 = NE == 1 ? 0 : b_sta2;
+  const BeamRow br = beam_row(EJ || beam != nullptr, r, pairs, Nbase, Ktot,
+                              NE);
   const double ur = u[r], vr = v[r], wr = w[r];
   const float blf = (float)(sqrt(ur * ur + vr * vr + wr * wr) * freq);
   const float uf = (float)(ur * freq), vf = (float)(vr * freq),
@@ -309,27 +352,17 @@ __device__ __forceinline__ void shapelet_coh_body(
   const float* rec0 = rec;          // sqrt(2/n)
   const float* rec1 = rec + nmax;   // sqrt((n-1)/n)
 
-  cf aI = {0.f, 0.f}, aQ = {0.f, 0.f}, aU = {0.f, 0.f}, aV = {0.f, 0.f};
-  // with EJ: the four coherency entries themselves
+  // sums of add_source, as in k_predict_coh
   cf acc[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
   auto flush = [&](int ci) {
     float2* o = out + ((size_t)ci * R + r) * 4;
-    if constexpr (EJ) {
-      for (int i = 0; i < 4; ++i) o[i] = cadd(o[i], acc[i]);
-      return;
-    }
-    // Stokes -> coherency [[I+Q, U+jV],[U-jV, I-Q]] (predict.c:228-235)
-    o[0] = cadd(o[0], cadd(aI, aQ));
-    o[1] = cadd(o[1], {aU.x - aV.y, aU.y + aV.x});
-    o[2] = cadd(o[2], {aU.x + aV.y, aU.y - aV.x});
-    o[3] = cadd(o[3], csub(aI, aQ));
+    put_coherency<EJ>(acc, [&](int i, cf c) { o[i] = cadd(o[i], c); });
   };
   int cur = cluster[0];
   for (int s = 0; s < S; ++s) {
     const int ci = cluster[s];
     if (ci != cur) {
       flush(cur);
-      aI = {0.f, 0.f}; aQ = {0.f, 0.f}; aU = {0.f, 0.f}; aV = {0.f, 0.f};
       for (int i = 0; i < 4; ++i) acc[i] = {0.f, 0.f};
       cur = ci;
     }
@@ -373,42 +406,37 @@ __device__ __forceinline__ void shapelet_coh_body(
       else        { re += pv * se; im += pv * so; }
     }
     phc = cmul(phc, {re, im});
-    if constexpr (EJ) {
-      const size_t tk = b_toff + (size_t)src[s];
-      float g = 1.0f;
-      if (beam != nullptr) {
-        const float* bg = beam + tk * (size_t)Nsta;
-        g = bg[b_sta1] * bg[b_sta2];
-      }
-      const cf* ej = ejones + tk * (size_t)NE * 4;
-      ej_accumulate(phc, flux[s], flux[S + s], flux[2 * S + s],
-                    flux[3 * S + s], g, ej + 4 * e_sta1, ej + 4 * e_sta2,
-                    acc);
-      continue;
-    }
-    if (beam != nullptr) {
-      const float* bg = beam + (b_toff + (size_t)src[s]) * (size_t)Nsta;
-      phc = cscale(phc, bg[b_sta1] * bg[b_sta2]);
-    }
-    aI = cadd(aI, cscale(phc, flux[s]));
-    aQ = cadd(aQ, cscale(phc, flux[S + s]));
-    aU = cadd(aU, cscale(phc, flux[2 * S + s]));
-    aV = cadd(aV, cscale(phc, flux[3 * S + s]));
+    add_source<EJ>(phc, [&](int i) { return flux[i * S + s]; }, src[s], br,
+                   beam, Nsta, ejones, NE, acc);
   }
   flush(cur);
 }
 
+// The one place that unpacks the argument structs of this kernel family.
+template <bool EJ>
+__device__ __forceinline__ void shapelet_coh_kernel(
+    const RowsUVW& rows, const ShapeletTab& t, const Channel& ch,
+    const BeamArgs& bm, float2* out) {
+  shapelet_coh_body<EJ>(
+      rows.u, rows.v, rows.w, rows.R, t.src, t.cluster, t.n0, t.beta, t.off,
+      t.coef, t.cxi, t.sxi, t.cphi, t.sphi, t.psign, t.a, t.b, t.ceP, t.seP,
+      t.ll, t.mm, t.nn1, t.rec, t.S, t.nmax, t.flux, t.r1, ch.freq,
+      ch.fdelta2, ch.tdelta, bm.beam, bm.pairs, bm.Nbase, bm.Ktot, bm.Nsta,
+      EJ ? bm.ejones : nullptr, EJ ? bm.NE : 0, out);
+}
+
 extern "C" __global__ void __launch_bounds__(128)
-k_shapelet_coh(SHAPELET_COH_PARAMS, float2* out) {
-  shapelet_coh_body<false>(SHAPELET_COH_ARGS, nullptr, 0, out);
+k_shapelet_coh(RowsUVW rows, ShapeletTab tab, Channel ch, BeamArgs bm,
+               float2* out) {
+  shapelet_coh_kernel<false>(rows, tab, ch, bm, out);
 }
 
 // E-Jones variant: E is indexed by the table's source index src[s], like
 // the beam; pairs, Nbase and Ktot are required, beam may be null.
 extern "C" __global__ void __launch_bounds__(128)
-k_shapelet_coh_ej(SHAPELET_COH_PARAMS, const float2* __restrict__ ejones,
-                  int NE, float2* out) {
-  shapelet_coh_body<true>(SHAPELET_COH_ARGS, ejones, NE, out);
+k_shapelet_coh_ej(RowsUVW rows, ShapeletTab tab, Channel ch, BeamArgs bm,
+                  float2* out) {
+  shapelet_coh_kernel<true>(rows, tab, ch, bm, out);
 }
 
 // Array-factor gains of every station toward every (timeslot, source), the

@@ -424,16 +424,11 @@ def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
     return out.view(gp.M, -1, 2, 2)
 
 
-def array_beam_gains(elem, nelem, du, below, freq):
-    """Station array-factor gains on the device (k_array_beam):
-      gain[t,k,n] = below[t,k] ? 0
-                  : |(1/nelem[n]) sum_e exp(i 2 pi f/c elem[n,e] . du[t,k])|
-    elem [N, Emax, 3] float64 ENU offsets, zero-padded, on the device the
-    gains are wanted on; nelem [N] element counts, each >= 1; du [T, K, 3]
-    float64 source minus pointing direction; below [T, K] bool/uint8.
-    Returns [T, K, N] float32, the `beam` argument of predict_coh."""
+def _beam_geometry_args(elem, nelem, du, below):
+    """Checks the arguments array_beam_gains and station_beam_gains share
+    and returns them as the extension wants them: (elem float64, nelem
+    int32, du float64, below uint8), contiguous on elem's device."""
     import numpy as np
-    from ..constants import C_LIGHT
     if not torch.is_tensor(elem) or not elem.is_cuda:
         raise ValueError("elem must be a device tensor [N, Emax, 3]")
     if elem.dim() != 3 or elem.shape[2] != 3 or elem.shape[1] < 1:
@@ -451,11 +446,23 @@ def array_beam_gains(elem, nelem, du, below, freq):
     if du.dim() != 3 or du.shape[2] != 3 \
             or tuple(below.shape) != tuple(du.shape[:2]):
         raise ValueError("du must be [T, K, 3] and below [T, K]")
+    return (elem.to(torch.float64).contiguous(),
+            torch.as_tensor(ne.astype(np.int32)).to(dev),
+            du.to(device=dev, dtype=torch.float64).contiguous(),
+            below.to(device=dev, dtype=torch.uint8).contiguous())
+
+
+def array_beam_gains(elem, nelem, du, below, freq):
+    """Station array-factor gains on the device (k_array_beam):
+      gain[t,k,n] = below[t,k] ? 0
+                  : |(1/nelem[n]) sum_e exp(i 2 pi f/c elem[n,e] . du[t,k])|
+    elem [N, Emax, 3] float64 ENU offsets, zero-padded, on the device the
+    gains are wanted on; nelem [N] element counts, each >= 1; du [T, K, 3]
+    float64 source minus pointing direction; below [T, K] bool/uint8.
+    Returns [T, K, N] float32, the `beam` argument of predict_coh."""
+    from ..constants import C_LIGHT
     return _ext().array_beam_gains(
-        elem.to(torch.float64).contiguous(),
-        torch.as_tensor(ne.astype(np.int32)).to(dev),
-        du.to(device=dev, dtype=torch.float64).contiguous(),
-        below.to(device=dev, dtype=torch.uint8).contiguous(),
+        *_beam_geometry_args(elem, nelem, du, below),
         2.0 * math.pi * float(freq) / C_LIGHT)
 
 
@@ -473,23 +480,8 @@ def station_beam_gains(elem, nelem, du, below, freqs, tile=None,
     the `beam` argument of predict_coh at freqs[f]."""
     import numpy as np
     from ..constants import C_LIGHT
-    if not torch.is_tensor(elem) or not elem.is_cuda:
-        raise ValueError("elem must be a device tensor [N, Emax, 3]")
-    if elem.dim() != 3 or elem.shape[2] != 3 or elem.shape[1] < 1:
-        raise ValueError("elem must be [N, Emax, 3]")
-    dev = elem.device
-    N, Emax = int(elem.shape[0]), int(elem.shape[1])
-    ne = np.asarray(nelem.cpu() if torch.is_tensor(nelem) else nelem)
-    if ne.shape != (N,):
-        raise ValueError(f"nelem must be [{N}]")
-    if (ne < 1).any() or (ne > Emax).any():
-        raise ValueError("every station needs 1 <= nelem <= Emax elements, "
-                         f"got {ne.tolist()}")
-    du = torch.as_tensor(du)
-    below = torch.as_tensor(below)
-    if du.dim() != 3 or du.shape[2] != 3 \
-            or tuple(below.shape) != tuple(du.shape[:2]):
-        raise ValueError("du must be [T, K, 3] and below [T, K]")
+    elem, ne, du, below = _beam_geometry_args(elem, nelem, du, below)
+    dev, N = elem.device, int(elem.shape[0])
     fq = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
     if fq.ndim != 1 or fq.size < 1:
         raise ValueError("freqs must be [F], F >= 1")
@@ -509,10 +501,7 @@ def station_beam_gains(elem, nelem, du, below, freqs, tile=None,
             tile=tile.to(torch.float64).contiguous(),
             du_tile=du_tile.to(device=dev, dtype=torch.float64).contiguous())
     return _ext().station_beam_gains(
-        elem.to(torch.float64).contiguous(),
-        torch.as_tensor(ne.astype(np.int32)).to(dev),
-        du.to(device=dev, dtype=torch.float64).contiguous(),
-        below.to(device=dev, dtype=torch.uint8).contiguous(),
+        elem, ne, du, below,
         torch.as_tensor(2.0 * math.pi * fq / C_LIGHT).to(dev), **kw)
 
 

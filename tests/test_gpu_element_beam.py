@@ -262,3 +262,55 @@ def test_argument_checks(sky):
     below = torch.zeros(T, K, dtype=torch.uint8)
     with pytest.raises(ValueError):           # a station with no elements
         hip_host.array_beam_gains(elem, np.array([4, 0]), du, below, S.FREQ0)
+
+
+def test_extension_rejects_malformed_beam(sky):
+    """The extension's predict_coh and shapelet_coh_add, called directly
+    (hip_host casts and slices before it calls them), refuse a beam or a
+    pair table the kernels would index out of bounds: 3 stations, 1
+    timeslot, 2 point sources, R = 3 rows. Each call returns before any
+    launch. shapelet_coh_add gets the mode table of the module's sky; its
+    checks never get as far as relating the table to the beam."""
+    ext = hip_host._ext()
+    dev = torch.device(DEV)
+    pack, _ = S.make_pack(spec=(), M=2, nsrc=1)
+    gp = hip_host.gpu_pack(pack, dev)
+    assert gp.K == 2 and gp.sh is None and not bool(gp.stype.any())
+    u, v, w = (x[:3].contiguous() for x in sky['uvw_d'])
+    Nbase = 3
+    pairs = torch.tensor([[0, 1], [0, 2], [1, 2]], dtype=torch.int32,
+                         device=dev)
+    beam = torch.full((1, 2, 3), 0.5, dtype=torch.float32, device=dev)
+    sI, sQ, sU, sV = gp.fluxes_at(S.FREQ0, S.FREQ0)
+    r1 = gp.r1_for(S.DEC0)
+    chan = (S.FREQ0, S.FDELTA * 0.5, S.TDELTA)
+
+    def predict(beam, pairs):
+        return ext.predict_coh(
+            u, v, w, gp.ll, gp.mm, gp.nn1, sI, sQ, sU, sV, gp.eX, gp.eY,
+            gp.eP, gp.cxi, gp.sxi, gp.cphi, gp.sphi, r1, gp.stype,
+            gp.cluster_off, *chan, beam=beam, pairs=pairs, Nbase=Nbase)
+
+    sgp = hip_host.gpu_pack(sky['pack'], dev)
+    tab = sgp.sh
+    flux = sgp.shapelet_fluxes_at(S.FREQ0, S.FREQ0)
+    r1s = sgp.r1_for(S.DEC0).index_select(0, tab.src)
+    out = torch.zeros(sgp.M, 3, 4, dtype=torch.complex64, device=dev)
+
+    def shapelet_add(beam, pairs):
+        ext.shapelet_coh_add(
+            out, u, v, w, *(getattr(tab, k) for k in tab.FIELDS), flux, r1s,
+            *chan, beam=beam, pairs=pairs, Nbase=Nbase)
+
+    assert predict(beam, pairs).shape == (2, 3, 4)    # the inputs are sound
+    bad = {'float64 beam': (beam.double(), pairs),
+           'CPU beam': (beam.cpu(), pairs),
+           'T*Nbase < R': (beam[:0].contiguous(), pairs),
+           '2*Nbase - 1 pair entries': (beam, pairs.reshape(-1)[:5]
+                                        .contiguous())}
+    for call in (predict, shapelet_add):
+        for what, (b, p) in bad.items():
+            with pytest.raises(RuntimeError):
+                call(b, p)
+                pytest.fail(f'{call.__name__} accepted a {what}')
+    assert not bool(out.any())                        # nothing was added

@@ -1,5 +1,6 @@
-// Torch-free standalone validator for the two round-2 gated kernels,
-// runnable inside a ~60 s gpurun window (no python/torch startup):
+// Torch-free standalone validator for two kernel paths, done in about a
+// minute (no python/torch startup). It calls the launchers through the
+// argument structs of launchers.h, as bindings.cpp does:
 //   1. k_cholmw_panel_big — chunked-panel Cholesky at n=4096
 //      (and n=512 through the same harness as a control)
 //   2. k_predict_coh beam argument — all-ones beam must reproduce the
@@ -121,15 +122,23 @@ static int test_beam_predict() {
   CHK(hipMalloc(&o0, sizeof(float2) * M * R * 4));
   CHK(hipMalloc(&o1, sizeof(float2) * M * R * 4));
   CHK(hipMalloc(&o2, sizeof(float2) * M * R * 4));
-  CHK(launch_predict_coh(du, dv, dw, dll, dmm, dnn, dsI, dsQ, dsU, dsV,
-      deX, deY, deP, dcxi, dsxi, dcphi, dsphi, dr1, dstype, dcoff, M, R,
-      freq, fdelta2, tdelta, nullptr, nullptr, 0, 0, 0, o0, 0));
-  CHK(launch_predict_coh(du, dv, dw, dll, dmm, dnn, dsI, dsQ, dsU, dsV,
-      deX, deY, deP, dcxi, dsxi, dcphi, dsphi, dr1, dstype, dcoff, M, R,
-      freq, fdelta2, tdelta, dbeam1, dpairs, Nbase, K, N, o1, 0));
-  CHK(launch_predict_coh(du, dv, dw, dll, dmm, dnn, dsI, dsQ, dsU, dsV,
-      deX, deY, deP, dcxi, dsxi, dcphi, dsphi, dr1, dstype, dcoff, M, R,
-      freq, fdelta2, tdelta, dbeam2, dpairs, Nbase, K, N, o2, 0));
+  RowsUVW rows = {};
+  rows.u = du; rows.v = dv; rows.w = dw; rows.R = R;
+  SourceArrays src = {};
+  src.ll = dll; src.mm = dmm; src.nn1 = dnn;
+  src.sI = dsI; src.sQ = dsQ; src.sU = dsU; src.sV = dsV;
+  src.eX = deX; src.eY = deY; src.eP = deP;
+  src.cxi = dcxi; src.sxi = dsxi; src.cphi = dcphi; src.sphi = dsphi;
+  src.r1 = dr1; src.stype = dstype; src.cluster_off = dcoff; src.M = M;
+  const Channel ch = {freq, fdelta2, tdelta};
+  BeamArgs nobeam = {}, bm1 = {}, bm2 = {};
+  bm1.beam = dbeam1; bm1.pairs = dpairs;
+  bm1.Nbase = Nbase; bm1.Ktot = K; bm1.Nsta = N;
+  bm2 = bm1;
+  bm2.beam = dbeam2;
+  CHK(launch_predict_coh(rows, src, ch, nobeam, o0, 0));
+  CHK(launch_predict_coh(rows, src, ch, bm1, o1, 0));
+  CHK(launch_predict_coh(rows, src, ch, bm2, o2, 0));
   CHK(hipDeviceSynchronize());
   std::vector<float2> h0(M * R * 4), h1(M * R * 4), h2(M * R * 4);
   CHK(hipMemcpy(h0.data(), o0, sizeof(float2) * h0.size(),
