@@ -198,6 +198,30 @@ def _elem_coeffs(args, z):
     return None if et == 'synthetic' else et     # name -> LOFAR tables
 
 
+def _channel_ejones(pack, tile, geom, tmjd, freq, coeffs):
+    """Element E-Jones [T, K, 2, 2] of one channel of the tile. Like
+    _channel_gains: the patterns of ALL the tile's channels come from one
+    batched evaluation (one kernel launch on the GPU for the LOFAR tables),
+    made once per tile and kept on it; a frequency that is not one of the
+    tile's channels is evaluated on its own. `coeffs` is what _elem_coeffs
+    returns, a table name or None, and is part of the key."""
+    from .. import beams
+    freqs = tuple(float(f) for f in tile.freqs)
+    if float(freq) not in freqs:
+        return beams.element_jones_channels(coeffs, geom, [float(freq)],
+                                            tile.u.device)[0]
+    key = _beam_key(pack, tmjd) + (freqs, coeffs)
+    memo = getattr(tile, '_beam_ejones', None)
+    if memo is None or memo[0] != key:
+        memo = (key, beams.element_jones_channels(coeffs, geom, freqs,
+                                                  tile.u.device))
+        try:
+            tile._beam_ejones = memo
+        except AttributeError:
+            pass
+    return memo[1][freqs.index(float(freq))]
+
+
 def _predict_with_beam(ms, pack, tile, ti, args):
     """Coherencies with the station beam applied (-B 1..6;
     predict_visibilities_multifreq_withbeam role). The MS must carry the
@@ -227,11 +251,13 @@ def _predict_with_beam(ms, pack, tile, ti, args):
     for f in tile.freqs:
         gains = _channel_gains(pack, tile, cfg, geom, tmjd, f) \
             if mode in (1, 2) else None
+        ej = _channel_ejones(pack, tile, geom, tmjd, f, coeffs) \
+            if mode in (2, 3) else None
         c = beams.predict_coh_withbeam(
             pack, tile.u, tile.v, tile.w, float(f), tile.freq0,
             fdelta_ch, tile.tdelta, tile.dec0, cfg, tmjd,
             ms.bb_tensor(), ms.Nbase, T, mode=mode, coeffs=coeffs,
-            geom=geom, gains=gains)
+            geom=geom, gains=gains, ejones=ej)
         acc = c if acc is None else acc + c
     return acc / len(tile.freqs)
 
@@ -250,10 +276,13 @@ def _predict_channel_with_beam(ms, pack, tile, ti, args, freq,
     geom = _beam_geometry(pack, tile, cfg, tmjd)
     gains = _channel_gains(pack, tile, cfg, geom, tmjd, freq) \
         if mode in (1, 2) else None
+    coeffs = _elem_coeffs(args, z)
+    ej = _channel_ejones(pack, tile, geom, tmjd, freq, coeffs) \
+        if mode in (2, 3) else None
     return beams.predict_coh_withbeam(
         pack, tile.u, tile.v, tile.w, freq, tile.freq0, fdelta_ch,
         tile.tdelta, tile.dec0, cfg, tmjd, ms.bb_tensor(), ms.Nbase, T,
-        mode=mode, coeffs=_elem_coeffs(args, z), geom=geom, gains=gains)
+        mode=mode, coeffs=coeffs, geom=geom, gains=gains, ejones=ej)
 
 
 def uv_flags(tile, args):

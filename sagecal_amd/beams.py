@@ -546,13 +546,38 @@ def element_jones(coeffs, geom, freq):
     return E.reshape(geom.T, geom.K, 2, 2)
 
 
+def element_jones_channels(coeffs, geom, freqs, device='cpu'):
+    """Dipole E-Jones of every (timeslot, source) of `geom` at every
+    frequency of `freqs` in one call: [F, T, K, 2, 2]; row f is
+    element_jones(coeffs, geom, freqs[f]). On the CPU it is exactly that
+    stack (complex128, the fp64 yardstick). On a CUDA device the real tables
+    (LofarElementCoeffs) are evaluated by one k_element_beam launch
+    (complex64); the synthetic spherical-harmonic ElementCoeffs has no
+    device kernel and is evaluated on the host, cast and copied."""
+    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    if freqs.ndim != 1 or freqs.size < 1:
+        raise ValueError("freqs must be [F], F >= 1")
+    # a table name or None (synthetic) is resolved once, as
+    # predict_coh_withbeam does per call: the synthetic table built for None
+    # has one frequency node, so it does not depend on which channel's
+    # frequency it is built with
+    coeffs = _resolve_coeffs(coeffs, float(freqs[0]))
+    on_gpu = torch.device(device).type == 'cuda'
+    if on_gpu and isinstance(coeffs, LofarElementCoeffs):
+        from .ops import hip_host
+        return hip_host.element_jones(coeffs, geom.az, geom.el, freqs,
+                                      device=device)
+    E = torch.stack([element_jones(coeffs, geom, float(f)) for f in freqs])
+    return E.to(torch.complex64).to(device) if on_gpu else E
+
+
 # ---------------------------------------------------------------------------
 # Beam-aware predict (CPU/torch; predict_withbeam.c analog)
 # ---------------------------------------------------------------------------
 
 def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
                          cfg, tmjd, bb, Nbase, T, mode=1, coeffs=None,
-                         geom=None, gains=None):
+                         geom=None, gains=None, ejones=None):
     """Coherencies with the station beam applied per source/station
     (precalculate_coherencies_withbeam semantics, Dirac_radio.h:471):
     C'_pq(src) = g_p(src) C g_q(src)^* for the scalar array factor
@@ -567,10 +592,11 @@ def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
     On a GPU tensor every mode is ONE hip_host.predict_coh call
     (kernel_array_beam / kernel_element_beam -> kernel_coherencies
     structure): the gains of modes 1 and 2 come from k_array_beam
-    (k_station_beam for a two-stage config), the host-evaluated element
-    E-Jones of modes 2 and 3 is applied per source inside the predict
-    kernels. On the CPU the per-source torch loop below is the fp64
-    yardstick for that path.
+    (k_station_beam for a two-stage config), the element E-Jones of modes 2
+    and 3 from k_element_beam for the real tables (from the host for the
+    synthetic pattern, element_jones_channels) and is applied per source
+    inside the predict kernels. On the CPU the per-source torch loop below
+    is the fp64 yardstick for that path.
 
     `geom`: the BeamGeometry of (pack, cfg, tmjd) when the caller already
     has it (per-channel loops build it once per tile); it does not change
@@ -582,6 +608,10 @@ def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
     caller already has them (one row of a station_beam_gains batch); used
     in modes 1 and 2 in place of computing them here. Mode 3 does not
     depend on the beamformer type (stationbeam.c:324-352).
+
+    `ejones`: the counterpart of `gains` for modes 2 and 3, the element
+    E-Jones [T, K, 2, 2] at `freq` when the caller already has it (one row
+    of an element_jones_channels batch); `coeffs` is then not read.
     """
     from .ops import reference as R
     B = u.shape[0]
@@ -596,7 +626,7 @@ def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
     use_elem = mode in (2, 3)
     if geom is None:
         geom = beam_geometry(cfg, *_pack_radec(pack, dec0), tmjd)
-    if use_elem:
+    if use_elem and ejones is None:
         coeffs = _resolve_coeffs(coeffs, freq)
     if u.is_cuda and (use_array or use_elem):
         # device path: no per-source loop; a missing extension raises
@@ -606,8 +636,13 @@ def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
             beam_t = array_beam_gains(cfg, geom, freq, u.device) \
                 if gains is None else \
                 gains.to(device=u.device, dtype=torch.float32)
-        ej = element_jones(coeffs, geom, freq).to(torch.complex64) \
-            .unsqueeze(2).to(u.device) if use_elem else None
+        ej = None
+        if use_elem:
+            if ejones is None:
+                ejones = element_jones_channels(coeffs, geom, [freq],
+                                                u.device)[0]
+            ej = ejones.to(device=u.device,
+                           dtype=torch.complex64).unsqueeze(2)
         return hip_host.predict_coh(
             pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
             beam=beam_t, pairs=bb, Nbase=Nbase, ejones=ej).to(cdtype)
@@ -620,7 +655,9 @@ def predict_coh_withbeam(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
         af = _array_factor(cfg, geom, [freq])        # [S, K, T, 1]
         af = af[..., 0].abs()                        # [S, K, T] real
     out = torch.zeros(M, B, 2, 2, dtype=cdtype, device=u.device)
-    if use_elem:
+    if use_elem and ejones is not None:
+        Ej = ejones.to(device=u.device, dtype=cdtype).transpose(0, 1)
+    elif use_elem:
         # element E-Jones per (source, time): one dipole pattern per
         # array origin (kernel_element_beam; DOBEAM_ELEMENT/FULL modes)
         Es = []

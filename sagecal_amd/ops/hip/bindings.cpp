@@ -269,6 +269,45 @@ torch::Tensor station_beam_gains(
   return gain;
 }
 
+// E[f,d] of k_element_beam: az, el [D] float64 directions, coef
+// [F, 2, Nmodes] complex64 theta and phi coefficient rows per frequency,
+// preamble [Nmodes] float32, Nmodes = M(M+1)/2 with 1 <= M <=
+// ELEMENT_BEAM_MAX_M, beta > 0. Returns [F, D, 2, 2] complex64.
+torch::Tensor element_jones(
+    torch::Tensor az, torch::Tensor el, torch::Tensor coef,
+    torch::Tensor preamble, int64_t M, double beta) {
+  TORCH_CHECK(M >= 1 && M <= ELEMENT_BEAM_MAX_M, "M must be 1..",
+              ELEMENT_BEAM_MAX_M, ", got ", M);
+  TORCH_CHECK(beta > 0.0 && (float)beta > 0.f, "beta must be positive");
+  const int64_t Nmodes = M * (M + 1) / 2;
+  TORCH_CHECK(az.is_cuda() && az.scalar_type() == torch::kDouble &&
+              az.is_contiguous() && az.dim() == 1,
+              "az must be contiguous [D] float64 on the device");
+  TORCH_CHECK(el.device() == az.device() &&
+              el.scalar_type() == torch::kDouble && el.is_contiguous() &&
+              el.dim() == 1 && el.size(0) == az.size(0),
+              "el must be contiguous [D] float64 like az");
+  TORCH_CHECK(coef.device() == az.device() &&
+              coef.scalar_type() == torch::kComplexFloat &&
+              coef.is_contiguous() && coef.dim() == 3 && coef.size(0) >= 1 &&
+              coef.size(1) == 2 && coef.size(2) == Nmodes,
+              "coef must be contiguous [F, 2, M(M+1)/2] complex64, F >= 1");
+  TORCH_CHECK(preamble.device() == az.device() &&
+              preamble.scalar_type() == torch::kFloat &&
+              preamble.is_contiguous() && preamble.dim() == 1 &&
+              preamble.size(0) == Nmodes,
+              "preamble must be contiguous [M(M+1)/2] float32");
+  const int64_t D = az.size(0), F = coef.size(0);
+  TORCH_CHECK(D < (int64_t(1) << 31) && F < (int64_t(1) << 31),
+              "too many directions or frequencies");
+  auto E = torch::empty({F, D, 2, 2},
+      torch::dtype(torch::kComplexFloat).device(az.device()));
+  CHECK_HIP(launch_element_beam(az.data_ptr<double>(), el.data_ptr<double>(),
+      ccptr(coef), preamble.data_ptr<float>(), (int)D, (int)F, (int)M,
+      (float)beta, cptr(E), cur_stream()));
+  return E;
+}
+
 std::vector<torch::Tensor> jtj_jtr(
     torch::Tensor x, torch::Tensor coh, torch::Tensor J,
     torch::Tensor pairs, torch::Tensor chunk_tab, torch::Tensor pidx,
@@ -437,6 +476,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("elem"), py::arg("nelem"), py::arg("du"), py::arg("below"),
         py::arg("kf"), py::arg("tile") = py::none(),
         py::arg("du_tile") = py::none());
+  m.def("element_jones", &element_jones,
+        "dipole element E-Jones [F, D, 2, 2] (gfx950)", py::arg("az"),
+        py::arg("el"), py::arg("coef"), py::arg("preamble"), py::arg("M"),
+        py::arg("beta"));
+  m.attr("ELEMENT_BEAM_MAX_M") = ELEMENT_BEAM_MAX_M;
   m.def("jtj_jtr", &jtj_jtr, "fused JtJ/Jtr assembly (gfx950)");
   m.def("model_cost", &model_cost, "per-chunk model cost (gfx950)");
   m.def("apply_jones", &apply_jones, "model apply / residual (gfx950)");

@@ -83,6 +83,16 @@ hipError_t launch_station_beam(
     const double* kfs, int N, int Emax, int D, int TK, int F, float* gain,
     hipStream_t stream);
 
+// Dipole E-Jones E [F, D, 2, 2] of D directions (az, el fp64) at F
+// frequencies: coef [F, 2, Nmodes] theta and phi rows, preamble [Nmodes],
+// Nmodes = M(M+1)/2. hipErrorInvalidValue: M outside 1..ELEMENT_BEAM_MAX_M,
+// F < 1 or beta not positive.
+#define ELEMENT_BEAM_MAX_M 8
+hipError_t launch_element_beam(
+    const double* az, const double* el, const float2* coef,
+    const float* preamble, int D, int F, int M, float beta, float2* E,
+    hipStream_t stream);
+
 hipError_t launch_jtj_accum(
     const float2* x, const float2* coh, const float2* J, const int* pairs,
     const int* chunk_tab, const int* pidx, const float* wts, int Nbase,

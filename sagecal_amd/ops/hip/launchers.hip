@@ -5,6 +5,7 @@
 #include "predict.hip"
 #include "jtj.hip"
 #include "cholesky.hip"
+#include "element_beam.hip"
 
 // One thread per row in blocks of 128: the plain kernel, or with
 // bm.ejones the _ej one, which reads pairs on every row. The two take the
@@ -71,6 +72,21 @@ hipError_t launch_station_beam(
       dim3((TK + tb - 1) / tb, (unsigned)gy, (unsigned)gz), dim3(tb), 0,
       stream, elem, nelem, tile, du, du_tile, below, kfs, N, Emax, D, TK, F,
       gain);
+  return hipGetLastError();
+}
+
+// coef [F, 2, M(M+1)/2], preamble [M(M+1)/2], E [F, D, 2, 2]; the kernel
+// unrolls its mode loops to EB_MAX_M and divides by beta
+hipError_t launch_element_beam(
+    const double* az, const double* el, const float2* coef,
+    const float* preamble, int D, int F, int M, float beta, float2* E,
+    hipStream_t stream) {
+  if (M < 1 || M > EB_MAX_M || F < 1 || D < 0 || !(beta > 0.f))
+    return hipErrorInvalidValue;
+  if (D == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_element_beam, dim3((D + EB_TB - 1) / EB_TB),
+                     dim3(EB_TB), 0, stream, az, el, coef, preamble, D, F, M,
+                     beta, E);
   return hipGetLastError();
 }
 

@@ -505,6 +505,55 @@ def station_beam_gains(elem, nelem, du, below, freqs, tile=None,
         torch.as_tensor(2.0 * math.pi * fq / C_LIGHT).to(dev), **kw)
 
 
+def element_jones(coeffs, az, el, freqs, device=None):
+    """Dipole element E-Jones on the device at F frequencies in one launch
+    (k_element_beam). coeffs: a beams.LofarElementCoeffs; az, el: arrays or
+    tensors of equal shape S (rad); freqs [F] Hz, F >= 1. The coefficient
+    rows come from coeffs.at_freq in fp64 on the host (clamped at the table
+    edges, interpolated inside), so only the pattern sum runs on the
+    device. Returns [F, *S, 2, 2] complex64 laid out as
+    LofarElementCoeffs.eval: row 0 the X dipole (Etheta, Ephi), row 1 the Y
+    dipole, all four entries exactly zero where el < 0 (compared in fp64).
+    `device`: where to evaluate; by default the device of az if that is a
+    device tensor, else the current one."""
+    import numpy as np
+    ext = _ext()
+    M = int(coeffs.M)
+    if not 1 <= M <= ext.ELEMENT_BEAM_MAX_M:   # the kernel's unroll cap
+        raise ValueError(f"the element-beam kernel takes 1 <= M <= "
+                         f"{ext.ELEMENT_BEAM_MAX_M}, the table has M = {M}")
+    nm = M * (M + 1) // 2
+    theta, phi = np.asarray(coeffs.theta), np.asarray(coeffs.phi)
+    pre = np.asarray(coeffs.preamble)
+    if theta.ndim != 2 or theta.shape[1] != nm or phi.shape != theta.shape \
+            or pre.shape != (nm,):
+        raise ValueError(f"M = {M} needs coefficient arrays of width {nm}, "
+                         f"got theta {theta.shape}, phi {phi.shape}, "
+                         f"preamble {pre.shape}")
+    if not float(coeffs.beta) > 0.0:
+        raise ValueError("beta must be positive")
+    fq = np.atleast_1d(np.asarray(freqs, dtype=np.float64))
+    if fq.ndim != 1 or fq.size < 1:
+        raise ValueError("freqs must be [F], F >= 1")
+    if device is None:
+        device = az.device if torch.is_tensor(az) and az.is_cuda else 'cuda'
+    az = torch.as_tensor(az)
+    el = torch.as_tensor(el)
+    if az.shape != el.shape:
+        raise ValueError(f"az {tuple(az.shape)} and el {tuple(el.shape)} "
+                         "must have one shape")
+    coef = np.empty((fq.size, 2, nm), dtype=np.complex64)
+    for i, f in enumerate(fq):
+        coef[i, 0], coef[i, 1] = coeffs.at_freq(float(f))
+    prep = lambda x: x.to(device=device,
+                          dtype=torch.float64).contiguous().reshape(-1)
+    E = ext.element_jones(
+        prep(az), prep(el), torch.from_numpy(coef).to(device),
+        torch.from_numpy(pre.astype(np.float32)).to(device), M,
+        float(coeffs.beta))
+    return E.view(fq.size, *az.shape, 2, 2)
+
+
 class BaselineLayout:
     """Row-structure descriptor for the solver kernels: rows are
     seg*(T*Nbase) + t*Nbase + b with a fixed pair table. Built once per

@@ -19,10 +19,17 @@ work-equivalent single-stage call, on any tree, is `--elements` = tiles + 16
 (the same number of phasors per station). `--gain-channels F` also times
 the station gains of F channels: F single-frequency array_beam_gains calls
 and, where the tree has it, one batched station_beam_gains call.
+`--element-channels F` times the dipole element E-Jones of F channels from
+the `--elem-type` table over the tool's timeslots x sources directions: the
+per-channel host loop (numpy pattern, cast to complex64, copy to the device;
+1 warm-up pass and 3 timed ones, each takes seconds) against one batched
+beams.element_jones_channels call on the device, upload of the directions
+included.
 
     python tools/bench_beam_predict.py --out result.json [--tree DIR]
         [--cpu-mode2 CALLS] [--sample sample.pt] [--modes 1,2,3]
         [--elements E] [--two-stage] [--gain-channels F]
+        [--element-channels F --elem-type {lba,hba,alo}]
 """
 import argparse
 import json
@@ -83,6 +90,11 @@ def main():
                     help='two-stage HBA stations: 16 dipoles per tile')
     ap.add_argument('--gain-channels', type=int, default=0, metavar='F',
                     help='also time the station gains of F channels')
+    ap.add_argument('--element-channels', type=int, default=0, metavar='F',
+                    help='also time the element E-Jones of F channels')
+    ap.add_argument('--elem-type', default='hba',
+                    choices=['lba', 'hba', 'alo'],
+                    help='coefficient table of --element-channels')
     args = ap.parse_args()
     tree = os.path.abspath(args.tree or os.path.join(
         os.path.dirname(os.path.abspath(__file__)), '..'))
@@ -110,13 +122,13 @@ def main():
             pack, *rows, FREQ0, FREQ0, FDELTA, TDELTA, DEC0, cfg, tmjd,
             pairs, Nbase, TSLOTS, mode=mode)
 
-    def timed(fn):
-        """Median-ready list of CALLS device-event timings of fn(), ms."""
-        for _ in range(WARMUP):
+    def timed(fn, warmup=WARMUP, calls=CALLS):
+        """Median-ready list of `calls` device-event timings of fn(), ms."""
+        for _ in range(warmup):
             out = fn()
         torch.cuda.synchronize()
         ms = []
-        for _ in range(CALLS):
+        for _ in range(calls):
             e0 = torch.cuda.Event(enable_timing=True)
             e1 = torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -154,6 +166,33 @@ def main():
             samples['gains'] = batch[:, ::7, ::13].cpu()
         else:
             samples['gains'] = torch.stack(rows)[:, ::7, ::13].cpu()
+
+    if args.element_channels > 0:
+        # element E-Jones alone, geometry prebuilt: the per-channel host
+        # evaluation against one batched device call; any exception ends
+        # the job
+        F = args.element_channels
+        co = beams.LofarElementCoeffs.load(args.elem_type)
+        fr = co.freqs_ghz * 1e9
+        freqs = np.linspace(fr[0], fr[-1], F + 2)[1:-1].tolist()
+        geom = beams.beam_geometry(cfg, *beams._pack_radec(pack, DEC0), tmjd)
+        res['element'] = {'channels': F, 'elem_type': args.elem_type,
+                          'freqs': freqs, 'directions': geom.T * geom.K}
+        ms, rows = timed(lambda: [
+            beams.element_jones(co, geom, f).to(torch.complex64).to(dev)
+            for f in freqs], warmup=1, calls=3)
+        res['element']['host_loop'] = dict(stats(ms), warmup=1, calls=3)
+        print(f'{tag} element E-Jones, {F} host evaluations + copies: '
+              f'median {np.median(ms):.1f} ms', flush=True)
+        ms, batch = timed(lambda: beams.element_jones_channels(
+            co, geom, freqs, dev))
+        res['element']['device_call'] = stats(ms)
+        rows = torch.stack(rows)
+        res['element']['device_vs_host_max_rel'] = float(
+            (batch - rows).abs().max() / rows.abs().max())
+        print(f'{tag} element E-Jones, one batched device call: median '
+              f'{np.median(ms):.3f} ms', flush=True)
+        samples['element'] = batch[:, ::7, ::13].cpu()
 
     for mode in [int(m) for m in args.modes.split(',') if m]:
         try:
