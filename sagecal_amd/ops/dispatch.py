@@ -75,6 +75,64 @@ def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0, **kw):
                          **kw)
 
 
+def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
+                         reduce=None):
+    """Coherencies of every channel of `freqs`, [F, M, R, 2, 2], or with
+    reduce='mean' their mean over the channels [M, R, 2, 2]; fdelta is the
+    width of one channel. On the GPU one launch of the all-channels kernel
+    (no shapelet sources: ValueError); elsewhere the per-channel loop over
+    the fp64 reference."""
+    if _use_hip(u):
+        from . import hip_host
+        return hip_host.predict_coh_channels(pack, u, v, w, freqs, freq0,
+                                             fdelta, tdelta, dec0, reduce)
+    if reduce not in (None, 'mean'):
+        raise ValueError(f"reduce must be None or 'mean', got {reduce!r}")
+    cohs = [R.predict_coh(pack, u, v, w, float(f), freq0, fdelta, tdelta,
+                          dec0) for f in freqs]
+    if not cohs:
+        if reduce:
+            raise ValueError("the mean over no channels is undefined")
+        cd = torch.complex128 if u.dtype == torch.float64 \
+            else torch.complex64
+        return torch.empty((0, pack.M, u.shape[0], 2, 2), dtype=cd,
+                           device=u.device)
+    out = torch.stack(cohs)
+    return out.mean(dim=0) if reduce else out
+
+
+def residuals_multifreq(pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
+                        J, chunk_tab, pairs, subtract=None):
+    """x[f] - sum over clusters with subtract[ci] of J_p C_f J_q^H,
+    [F, R, 2, 2]. J [Mt, N, 2, 2] packed solutions; chunk_tab [M, T] global
+    chunk id per (cluster, timeslot); pairs [Nbase, 2], rows r = t*Nbase + b;
+    a row whose pair has a negative entry keeps x. On the GPU one launch of
+    the fused kernel (no shapelet sources: ValueError); elsewhere the
+    per-channel loop over R.predict_coh and R.apply_jones."""
+    if _use_hip(u):
+        from . import hip_host
+        return hip_host.residuals_multifreq(
+            pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0, J,
+            chunk_tab, pairs, subtract)
+    T, Nbase = int(chunk_tab.shape[1]), int(pairs.shape[0])
+    bb = pairs.to(device=x.device, dtype=torch.long).repeat(T, 1)
+    ok = (bb >= 0).all(dim=1)
+    bb = bb.clamp_min(0)
+    rows = chunk_tab.to(device=x.device,
+                        dtype=torch.long).repeat_interleave(Nbase, dim=1)
+    out = torch.empty_like(x)
+    for fi, f in enumerate(freqs):
+        cohs = R.predict_coh(pack, u, v, w, float(f), freq0, fdelta, tdelta,
+                             dec0).to(x.dtype)
+        V = torch.zeros_like(cohs[0])
+        for ci in range(cohs.shape[0]):
+            if subtract is not None and not bool(subtract[ci]):
+                continue
+            V = V + R.apply_jones(cohs[ci], J, bb, rows[ci])
+        out[fi] = torch.where(ok[:, None, None], x[fi] - V, x[fi])
+    return out
+
+
 def jtj_jtr(x, coh, J, bb, N, weights=None, chunk_rows=None, nchunk=1,
             layout=None):
     if _use_hip(x):

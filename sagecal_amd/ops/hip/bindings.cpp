@@ -180,6 +180,157 @@ void shapelet_coh_add(
                                 cur_stream()));
 }
 
+// The arguments the two all-channels entry points share, checked: every
+// per-source tensor has K entries, flux is [F, 4, K] float32 (I, Q, U, V
+// rows per channel), freqs [F] float64, all on u's device and contiguous.
+struct MfArgs {
+  RowsUVW rows;
+  SourceArrays src;
+  Channels ch;
+};
+
+static MfArgs mf_args(
+    const torch::Tensor& u, const torch::Tensor& v, const torch::Tensor& w,
+    const torch::Tensor& ll, const torch::Tensor& mm,
+    const torch::Tensor& nn1, const torch::Tensor& flux,
+    const torch::Tensor& eX, const torch::Tensor& eY,
+    const torch::Tensor& eP, const torch::Tensor& cxi,
+    const torch::Tensor& sxi, const torch::Tensor& cphi,
+    const torch::Tensor& sphi, const torch::Tensor& r1,
+    const torch::Tensor& stype, const torch::Tensor& cluster_off,
+    const torch::Tensor& freqs, double fdelta2, double tdelta) {
+  TORCH_CHECK(u.is_cuda() && u.dim() == 1, "u must be a device tensor [R]");
+  const int64_t R = u.size(0), K = ll.size(0);
+  auto chk = [&](const torch::Tensor& t, torch::ScalarType ty, int64_t n,
+                 const char* name) {
+    TORCH_CHECK(t.device() == u.device(), name, " is on another device");
+    TORCH_CHECK(t.scalar_type() == ty, name, " has the wrong dtype");
+    TORCH_CHECK(t.is_contiguous() && t.numel() == n, name,
+                " must be contiguous with ", n, " elements");
+  };
+  chk(u, torch::kDouble, R, "u");
+  chk(v, torch::kDouble, R, "v");
+  chk(w, torch::kDouble, R, "w");
+  chk(ll, torch::kDouble, K, "ll");
+  chk(mm, torch::kDouble, K, "mm");
+  chk(nn1, torch::kDouble, K, "nn1");
+  chk(eX, torch::kFloat, K, "eX");
+  chk(eY, torch::kFloat, K, "eY");
+  chk(eP, torch::kFloat, K, "eP");
+  chk(cxi, torch::kFloat, K, "cxi");
+  chk(sxi, torch::kFloat, K, "sxi");
+  chk(cphi, torch::kFloat, K, "cphi");
+  chk(sphi, torch::kFloat, K, "sphi");
+  chk(r1, torch::kFloat, K, "r1");
+  chk(stype, torch::kInt, K, "stype");
+  TORCH_CHECK(freqs.dim() == 1 && freqs.size(0) >= 1, "freqs must be [F], "
+              "F >= 1");
+  const int64_t F = freqs.size(0);
+  chk(freqs, torch::kDouble, F, "freqs");
+  TORCH_CHECK(flux.dim() == 3 && flux.size(0) == F && flux.size(1) == 4,
+              "flux must be [F, 4, K]");
+  chk(flux, torch::kFloat, F * 4 * K, "flux");
+  TORCH_CHECK(cluster_off.dim() == 1 && cluster_off.size(0) >= 1,
+              "cluster_off must be [M + 1]");
+  chk(cluster_off, torch::kInt, cluster_off.size(0), "cluster_off");
+  TORCH_CHECK(R >= 1 && R < (int64_t(1) << 31), "rows out of range");
+  MfArgs a = {};
+  a.rows = rows_uvw(u, v, w);
+  a.src.ll = dp(ll); a.src.mm = dp(mm); a.src.nn1 = dp(nn1);
+  a.src.sI = fp(flux); a.src.sQ = fp(flux) + K;
+  a.src.sU = fp(flux) + 2 * K; a.src.sV = fp(flux) + 3 * K;
+  a.src.eX = fp(eX); a.src.eY = fp(eY); a.src.eP = fp(eP);
+  a.src.cxi = fp(cxi); a.src.sxi = fp(sxi); a.src.cphi = fp(cphi);
+  a.src.sphi = fp(sphi); a.src.r1 = fp(r1);
+  a.src.stype = ip(stype); a.src.cluster_off = ip(cluster_off);
+  a.src.M = (int)cluster_off.size(0) - 1;
+  a.ch.freqs = dp(freqs);
+  a.ch.F = (int)F;
+  a.ch.fdelta2 = fdelta2;
+  a.ch.tdelta = tdelta;
+  a.ch.flux_stride = 4 * K;
+  return a;
+}
+
+// Coherencies of all F channels in one launch (k_predict_coh_mf):
+// [F, M, R, 4] complex64, or with mean their channel mean [M, R, 4]
+// (k_predict_coh_mean). The caller guarantees that cluster_off is
+// non-decreasing from 0 to K.
+torch::Tensor predict_coh_channels(
+    torch::Tensor u, torch::Tensor v, torch::Tensor w,
+    torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
+    torch::Tensor flux, torch::Tensor eX, torch::Tensor eY, torch::Tensor eP,
+    torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
+    torch::Tensor sphi, torch::Tensor r1, torch::Tensor stype,
+    torch::Tensor cluster_off, torch::Tensor freqs, double fdelta2,
+    double tdelta, bool mean) {
+  const MfArgs a = mf_args(u, v, w, ll, mm, nn1, flux, eX, eY, eP, cxi, sxi,
+                           cphi, sphi, r1, stype, cluster_off, freqs,
+                           fdelta2, tdelta);
+  auto copts = torch::dtype(torch::kComplexFloat).device(u.device());
+  auto out = mean ? torch::empty({a.src.M, a.rows.R, 4}, copts)
+                  : torch::empty({a.ch.F, a.src.M, a.rows.R, 4}, copts);
+  CHECK_HIP(launch_predict_coh_mf(a.rows, a.src, a.ch, mean ? 1 : 0,
+                                  cptr(out), cur_stream()));
+  return out;
+}
+
+// x - sum over clusters with skip == 0 of J_p C J_q^H for all F channels in
+// one launch (k_residual_mf): x [F, R, 4] complex64, J [Mt, N, 4]
+// complex64, chunk_tab [M, T] int32 global chunk ids, pairs [Nbase, 2]
+// int32, R == T * Nbase, skip [M] int32 or none. Returns [F, R, 4]. The
+// caller guarantees chunk ids below Mt and pair entries below N.
+torch::Tensor residuals_multifreq(
+    torch::Tensor x, torch::Tensor u, torch::Tensor v, torch::Tensor w,
+    torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
+    torch::Tensor flux, torch::Tensor eX, torch::Tensor eY, torch::Tensor eP,
+    torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
+    torch::Tensor sphi, torch::Tensor r1, torch::Tensor stype,
+    torch::Tensor cluster_off, torch::Tensor freqs, double fdelta2,
+    double tdelta, torch::Tensor J, torch::Tensor chunk_tab,
+    torch::Tensor pairs, c10::optional<torch::Tensor> skip) {
+  const MfArgs a = mf_args(u, v, w, ll, mm, nn1, flux, eX, eY, eP, cxi, sxi,
+                           cphi, sphi, r1, stype, cluster_off, freqs,
+                           fdelta2, tdelta);
+  const int64_t R = a.rows.R, F = a.ch.F, M = a.src.M;
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType ty) {
+    return t.device() == u.device() && t.scalar_type() == ty &&
+           t.is_contiguous();
+  };
+  TORCH_CHECK(on_dev(x, torch::kComplexFloat) && x.dim() == 3 &&
+              x.size(0) == F && x.size(1) == R && x.size(2) == 4,
+              "x must be contiguous [F, R, 4] complex64");
+  TORCH_CHECK(on_dev(J, torch::kComplexFloat) && J.dim() == 3 &&
+              J.size(0) >= 1 && J.size(1) >= 1 && J.size(2) == 4,
+              "J must be contiguous [Mt, N, 4] complex64");
+  TORCH_CHECK(on_dev(chunk_tab, torch::kInt) && chunk_tab.dim() == 2 &&
+              chunk_tab.size(0) == M && chunk_tab.size(1) >= 1,
+              "chunk_tab must be contiguous [M, T] int32");
+  TORCH_CHECK(on_dev(pairs, torch::kInt) && pairs.dim() == 2 &&
+              pairs.size(0) >= 1 && pairs.size(1) == 2,
+              "pairs must be contiguous [Nbase, 2] int32");
+  TORCH_CHECK(chunk_tab.size(1) * pairs.size(0) == R,
+              "rows must be T * Nbase");
+  ResidualArgs res = {};
+  res.x = ccptr(x);
+  res.J = ccptr(J);
+  res.chunk_tab = ip(chunk_tab);
+  res.pairs = ip(pairs);
+  if (skip.has_value()) {
+    TORCH_CHECK(on_dev(*skip, torch::kInt) && skip->numel() == M,
+                "skip must be contiguous [M] int32");
+    res.skip = ip(*skip);
+  }
+  res.Nbase = (int)pairs.size(0);
+  res.T = (int)chunk_tab.size(1);
+  res.N = (int)J.size(1);
+  auto out = torch::empty({F, R, 4},
+      torch::dtype(torch::kComplexFloat).device(u.device()));
+  CHECK_HIP(launch_residual_mf(a.rows, a.src, a.ch, res, cptr(out),
+                               cur_stream()));
+  return out;
+}
+
 // The four tensors both beam-gain entry points share: elem [N, Emax, 3]
 // float64 on the device, nelem [N] int32 (the caller has checked
 // 1 <= nelem <= Emax on the host), du [T, K, 3] float64, below [T, K] uint8.
@@ -468,6 +619,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tdelta"), py::arg("beam") = py::none(),
         py::arg("pairs") = py::none(), py::arg("Nbase") = 0,
         py::arg("ejones") = py::none(), py::arg("Nsta") = 0);
+  m.def("predict_coh_channels", &predict_coh_channels,
+        "coherency predict, all channels in one launch (gfx950)",
+        py::arg("u"), py::arg("v"), py::arg("w"), py::arg("ll"),
+        py::arg("mm"), py::arg("nn1"), py::arg("flux"), py::arg("eX"),
+        py::arg("eY"), py::arg("eP"), py::arg("cxi"), py::arg("sxi"),
+        py::arg("cphi"), py::arg("sphi"), py::arg("r1"), py::arg("stype"),
+        py::arg("cluster_off"), py::arg("freqs"), py::arg("fdelta2"),
+        py::arg("tdelta"), py::arg("mean") = false);
+  m.def("residuals_multifreq", &residuals_multifreq,
+        "predict and subtract, all channels in one launch (gfx950)",
+        py::arg("x"), py::arg("u"), py::arg("v"), py::arg("w"), py::arg("ll"),
+        py::arg("mm"), py::arg("nn1"), py::arg("flux"), py::arg("eX"),
+        py::arg("eY"), py::arg("eP"), py::arg("cxi"), py::arg("sxi"),
+        py::arg("cphi"), py::arg("sphi"), py::arg("r1"), py::arg("stype"),
+        py::arg("cluster_off"), py::arg("freqs"), py::arg("fdelta2"),
+        py::arg("tdelta"), py::arg("J"), py::arg("chunk_tab"),
+        py::arg("pairs"), py::arg("skip") = py::none());
+  m.attr("PREDICT_MF_NF") = PREDICT_MF_NF;
   m.def("array_beam_gains", &array_beam_gains,
         "station array-factor gains [T, K, N] (gfx950)", py::arg("elem"),
         py::arg("nelem"), py::arg("du"), py::arg("below"), py::arg("kf"));

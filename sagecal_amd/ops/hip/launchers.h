@@ -50,6 +50,27 @@ struct Channel {
   double tdelta;
 };
 
+// The F channels of the all-channels kernels (predict_mf.hip). With these
+// the flux pointers of SourceArrays address channel 0 of [F, K] arrays
+// whose rows lie flux_stride floats apart.
+struct Channels {
+  const double* freqs;      // [F], on the device
+  int F;
+  double fdelta2;           // channel halfwidth [Hz]
+  double tdelta;
+  long long flux_stride;
+};
+
+// What k_residual_mf takes besides the predict arguments.
+struct ResidualArgs {
+  const float2* x;          // [F, R, 4] data
+  const float2* J;          // [Mt, N, 4] packed solutions
+  const int* chunk_tab;     // [M, T] global chunk id, chunk_off[ci] added
+  const int* pairs;         // [Nbase, 2]; a negative entry keeps x
+  const int* skip;          // [M] non-zero: solved but not subtracted; or null
+  int Nbase, T, N;
+};
+
 // Station beam of both predict kernels. beam null: no scalar gain; ejones
 // null: the kernels without E-Jones run. pairs, Nbase and Ktot are read
 // with either; Nsta strides beam, NE (1 or Nsta) strides ejones.
@@ -70,6 +91,22 @@ hipError_t launch_predict_coh(RowsUVW rows, SourceArrays src, Channel ch,
                               BeamArgs bm, float2* out, hipStream_t stream);
 hipError_t launch_shapelet_coh(RowsUVW rows, ShapeletTab tab, Channel ch,
                                BeamArgs bm, float2* out, hipStream_t stream);
+
+// All channels in one launch, no beam and no shapelet sources (their
+// fluxes arrive zeroed). Channels a thread carries per pass:
+#ifndef PREDICT_MF_NF
+#define PREDICT_MF_NF 2
+#endif
+// out [F, M, R, 4], or with mean != 0 the channel mean [M, R, 4].
+// hipErrorInvalidValue: F < 1 or R < 1.
+hipError_t launch_predict_coh_mf(RowsUVW rows, SourceArrays src, Channels ch,
+                                 int mean, float2* out, hipStream_t stream);
+// out [F, R, 4] = x - sum over clusters with skip == 0 of J_p C J_q^H.
+// hipErrorInvalidValue: F < 1, R < 1, R != T * Nbase, or x, J, chunk_tab
+// or pairs missing.
+hipError_t launch_residual_mf(RowsUVW rows, SourceArrays src, Channels ch,
+                              ResidualArgs res, float2* out,
+                              hipStream_t stream);
 
 hipError_t launch_array_beam(
     const double* elem, const int* nelem, const double* du,

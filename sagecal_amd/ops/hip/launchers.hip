@@ -3,6 +3,7 @@
 #include "common.h"
 #include "launchers.h"
 #include "predict.hip"
+#include "predict_mf.hip"
 #include "jtj.hip"
 #include "cholesky.hip"
 #include "element_beam.hip"
@@ -38,6 +39,40 @@ hipError_t launch_shapelet_coh(RowsUVW rows, ShapeletTab tab, Channel ch,
   if (tab.S <= 0 || rows.R <= 0) return hipSuccess;
   return launch_rows(k_shapelet_coh, k_shapelet_coh_ej, rows, tab, ch, bm,
                      out, stream);
+}
+
+// blocks of 128 rows; passes of MF_NF channels along grid z except for the
+// mean, whose threads walk the passes themselves
+static bool mf_grid(int R, int F, bool z_passes, dim3* grid) {
+  if (F < 1 || R < 1) return false;
+  const long long gz = z_passes ? (F + MF_NF - 1) / MF_NF : 1;
+  if (gz > 65535) return false;
+  *grid = dim3((R + 127) / 128, 1, (unsigned)gz);
+  return true;
+}
+
+hipError_t launch_predict_coh_mf(RowsUVW rows, SourceArrays src, Channels ch,
+                                 int mean, float2* out, hipStream_t stream) {
+  dim3 grid;
+  if (!mf_grid(rows.R, ch.F, !mean, &grid) || ch.freqs == nullptr)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(mean ? k_predict_coh_mean : k_predict_coh_mf, grid,
+                     dim3(128), 0, stream, rows, src, ch, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_residual_mf(RowsUVW rows, SourceArrays src, Channels ch,
+                              ResidualArgs res, float2* out,
+                              hipStream_t stream) {
+  dim3 grid;
+  if (!mf_grid(rows.R, ch.F, true, &grid) || ch.freqs == nullptr ||
+      res.x == nullptr || res.J == nullptr || res.chunk_tab == nullptr ||
+      res.pairs == nullptr || res.Nbase < 1 || res.T < 1 || res.N < 1 ||
+      (long long)res.T * res.Nbase != rows.R)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_residual_mf, grid, dim3(128), 0, stream, rows, src,
+                     ch, res, out);
+  return hipGetLastError();
 }
 
 hipError_t launch_array_beam(

@@ -70,26 +70,42 @@ __device__ __forceinline__ void sincos_reduced(double ph, float* sp,
   __sincosf(phr, sp, cp);
 }
 
+// The pieces of phase_smear. Only the phase and the time smearing depend
+// on the channel; the all-channels kernels (predict_mf.hip) take the other
+// two once per source and row.
+// fp64 phase term G = 2*pi*(u l + v m + w (n-1)) (seconds * none)
+__device__ __forceinline__ double phase_term(double ur, double vr, double wr,
+                                             double l, double m, double n1) {
+  return 6.283185307179586476925286766559 * (ur * l + vr * m + wr * n1);
+}
+
+// freq smearing |sinc(G*fdelta/2)| (predict.c:178-189)
+__device__ __forceinline__ float freq_smear(double G, double fdelta2) {
+  float sm = 1.0f;
+  const float smf = (float)(G * fdelta2);
+  if (fabsf(smf) > 1e-9f) sm = fabsf(__sinf(smf) / smf);
+  return sm;
+}
+
+// sm times the time smearing (predict.c:94-107); r1 precomputed per source
+__device__ __forceinline__ float time_smear(float sm, float tsm_c, float r1) {
+  const float prod = tsm_c * r1;
+  if (prod > 1e-9f) sm *= 1.0645f * erff(0.8326f * prod) / prod;
+  return sm;
+}
+
 // Smeared phase term of one source at one row, shared by k_predict_coh and
 // k_shapelet_coh: exp(i*phase) * freq smearing * time smearing.
 __device__ __forceinline__ cf phase_smear(double ur, double vr, double wr,
                                           double l, double m, double n1,
                                           double freq, double fdelta2,
                                           float tsm_c, float r1) {
-  // fp64 phase term G = 2*pi*(u l + v m + w (n-1)) (seconds * none)
-  const double G = 6.283185307179586476925286766559 *
-      (ur * l + vr * m + wr * n1);
+  const double G = phase_term(ur, vr, wr, l, m, n1);
   // phase at this channel, arg-reduced in fp64 then fast float sincos
   const double ph = fma(G, freq, 0.0);
   float sp, cp;
   sincos_reduced(ph, &sp, &cp);
-  // freq smearing |sinc(G*fdelta/2)| (predict.c:178-189)
-  float sm = 1.0f;
-  const float smf = (float)(G * fdelta2);
-  if (fabsf(smf) > 1e-9f) sm = fabsf(__sinf(smf) / smf);
-  // time smearing (predict.c:94-107); r1 precomputed per source
-  const float prod = tsm_c * r1;
-  if (prod > 1e-9f) sm *= 1.0645f * erff(0.8326f * prod) / prod;
+  const float sm = time_smear(freq_smear(G, fdelta2), tsm_c, r1);
   return {cp * sm, sp * sm};
 }
 

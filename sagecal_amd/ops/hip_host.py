@@ -239,6 +239,7 @@ class GPUPack:
         self.freq0 = None
         self._flux_cache = {}
         self._sh_flux_cache = {}
+        self._stack_cache = {}
 
     def _flog(self, freq):
         """Log-polynomial spectral exponent per source at `freq`."""
@@ -277,6 +278,25 @@ class GPUPack:
         self._flux_cache[key] = out
         return out
 
+    def flux_stack(self, freqs, freq0):
+        """(fluxes [F, 4, K] float32, freqs [F] float64) on the device for
+        the all-channels kernels: row f stacks fluxes_at(freqs[f], freq0),
+        so a channel within 1 Hz of freq0 carries the pack fluxes and every
+        other one the spectral-index scaling of the catalogue fluxes.
+        Remembered per frequency tuple."""
+        key = (tuple(round(float(f), 3) for f in freqs),
+               round(float(freq0), 3))
+        hit = self._stack_cache.get(key)
+        if hit is None:
+            if len(self._stack_cache) > 16:   # bound long multi-MS runs
+                self._stack_cache.pop(next(iter(self._stack_cache)))
+            flux = torch.stack([torch.stack(self.fluxes_at(float(f), freq0))
+                                for f in freqs]).contiguous()
+            fq = torch.tensor([float(f) for f in freqs], dtype=torch.float64,
+                              device=self.ll.device)
+            hit = self._stack_cache[key] = (flux, fq)
+        return hit
+
     def shapelet_fluxes_at(self, freq, freq0):
         """Un-zeroed I, Q, U, V of the shapelet sources at channel `freq`,
         [4, S] float32 in table order."""
@@ -303,12 +323,13 @@ def gpu_pack(pack, device):
     return _gpu_pack_cache[key]
 
 
-_nsta_memo = {}      # (pairs token, version) -> (min, max) station index
+_nsta_memo = {}      # (table token, version) -> (min, max) entry
 
 
 def _pair_range(pairs):
-    """(min, max) station index of a device pair table. Reads it back to
-    the host, so the answer is remembered per tensor."""
+    """(min, max) entry of a device index table (station pairs, chunk
+    ids). Reads it back to the host, so the answer is remembered per
+    tensor."""
     try:
         key = (dispatch.obj_token(pairs), pairs._version)
     except RuntimeError:                 # inference tensor: no version
@@ -422,6 +443,104 @@ def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
                 flux, r1s, float(freq), float(fdelta) * 0.5, float(tdelta),
                 beam=beam, pairs=pairs, Nbase=int(Nbase), **ej)
     return out.view(gp.M, -1, 2, 2)
+
+
+def _mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0):
+    """Positional arguments u .. tdelta of the extension's all-channels
+    entry points."""
+    flux, fq = gp.flux_stack(freqs, freq0)
+    f64 = lambda t: t.to(torch.float64).contiguous()
+    return (f64(u), f64(v), f64(w), gp.ll, gp.mm, gp.nn1, flux, gp.eX,
+            gp.eY, gp.eP, gp.cxi, gp.sxi, gp.cphi, gp.sphi, gp.r1_for(dec0),
+            gp.stype, gp.cluster_off, fq, float(fdelta) * 0.5, float(tdelta))
+
+
+def _mf_pack(pack, device, what):
+    gp = pack if isinstance(pack, GPUPack) else gpu_pack(pack, device)
+    if gp.sh is not None:
+        raise ValueError(f"{what} has no shapelet sources; predict this "
+                         "pack channel by channel with predict_coh")
+    return gp
+
+
+def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
+                         reduce=None):
+    """Coherencies of every channel of `freqs` in one launch
+    (k_predict_coh_mf): [F, M, R, 2, 2] complex64, channel f equal to
+    predict_coh at freqs[f] without beam (bit for bit on point sources; an
+    extended source's envelope may round differently). reduce='mean' returns
+    their mean over the channels [M, R, 2, 2] instead (k_predict_coh_mean)
+    and never stores the channels; it needs at least one. fdelta is the
+    width of one channel. No station beam, no E-Jones; a pack with shapelet
+    sources raises ValueError. Empty freqs or no rows return an empty tensor
+    without a launch. Once the pack and the flux stack of this frequency
+    tuple are on the device the path has no host synchronisation."""
+    if reduce not in (None, 'mean'):
+        raise ValueError(f"reduce must be None or 'mean', got {reduce!r}")
+    gp = _mf_pack(pack, u.device, 'predict_coh_channels')
+    freqs = [float(f) for f in freqs]
+    F, R = len(freqs), int(u.shape[0])
+    if reduce == 'mean' and F == 0:
+        raise ValueError("the mean over no channels is undefined")
+    if F == 0 or R == 0:
+        shape = (gp.M, R, 2, 2) if reduce else (F, gp.M, R, 2, 2)
+        return torch.empty(shape, dtype=torch.complex64, device=u.device)
+    out = _ext().predict_coh_channels(
+        *_mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0),
+        mean=reduce == 'mean')
+    return out.view(*out.shape[:-1], 2, 2)
+
+
+def residuals_multifreq(pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
+                        J, chunk_tab, pairs, subtract=None):
+    """x[f] - sum over subtracted clusters of J_p C_f J_q^H for every
+    channel in one launch (k_residual_mf); the coherencies C_f are those of
+    predict_coh_channels and are never stored. x [F, R, 2, 2] complex; J
+    [Mt, N, 2, 2] packed solutions; chunk_tab [M, T] global chunk id of each
+    (cluster, timeslot), chunk_off[ci] included; pairs [Nbase, 2] stations
+    of the baselines, R = T * Nbase; subtract [M] booleans, False for a
+    cluster that is solved but stays in the residual (negative cluster id,
+    residual.c:74), default all True. A row whose pair has a negative entry
+    keeps x. Returns [F, R, 2, 2] complex64. The first call with a new pair
+    or chunk table reads its index range back for the bounds check; after
+    that, and once pack and flux stack are on the device, the path has no
+    host synchronisation."""
+    dev = u.device
+    gp = _mf_pack(pack, dev, 'residuals_multifreq')
+    freqs = [float(f) for f in freqs]
+    F, R = len(freqs), int(u.shape[0])
+    if x.dim() != 4 or tuple(x.shape) != (F, R, 2, 2):
+        raise ValueError(f"x must be [{F}, {R}, 2, 2], got {tuple(x.shape)}")
+    if F == 0 or R == 0:
+        return torch.empty((F, R, 2, 2), dtype=torch.complex64, device=dev)
+    if J.dim() != 4 or tuple(J.shape[2:]) != (2, 2):
+        raise ValueError("J must be [Mt, N, 2, 2]")
+    Mt, N = int(J.shape[0]), int(J.shape[1])
+    if chunk_tab.dim() != 2 or chunk_tab.shape[0] != gp.M:
+        raise ValueError(f"chunk_tab must be [{gp.M}, T]")
+    if pairs.dim() != 2 or pairs.shape[1] != 2 \
+            or chunk_tab.shape[1] * pairs.shape[0] != R:
+        raise ValueError("pairs must be [Nbase, 2] with T * Nbase rows")
+    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
+    chunk_tab, pairs = i32(chunk_tab), i32(pairs)
+    # the kernel indexes J by both tables with no checks of its own
+    if _pair_range(pairs)[1] >= N:
+        raise ValueError(f"pairs name a station outside the {N} of J")
+    lo, hi = _pair_range(chunk_tab)
+    if lo < 0 or hi >= Mt:
+        raise ValueError(f"chunk_tab names chunks {lo}..{hi}, J has {Mt}")
+    skip = None
+    if subtract is not None:
+        sub = torch.as_tensor(subtract).to(torch.bool)
+        if tuple(sub.shape) != (gp.M,):
+            raise ValueError(f"subtract must be [{gp.M}]")
+        skip = (~sub).to(device=dev, dtype=torch.int32).contiguous()
+    out = _ext().residuals_multifreq(
+        x.to(torch.complex64).reshape(F, R, 4).contiguous(),
+        *_mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0),
+        J.to(torch.complex64).reshape(Mt, N, 4).contiguous(), chunk_tab,
+        pairs, skip)
+    return out.view(F, R, 2, 2)
 
 
 def _beam_geometry_args(elem, nelem, du, below):

@@ -121,12 +121,62 @@ def precalc_coherencies(pack, tile, device=None, discrete=True):
         return ops.predict_coh(pack, u, v, w, tile.freq0, tile.freq0,
                                tile.fdelta, tile.tdelta, tile.dec0)
     fdelta_ch = tile.fdelta / len(freqs)
+    if _all_channels_ok(pack, u):
+        # one launch: the channels are summed in the kernel, none stored
+        return ops.predict_coh_channels(pack, u, v, w, freqs, tile.freq0,
+                                        fdelta_ch, tile.tdelta, tile.dec0,
+                                        reduce='mean')
     acc = None
     for f in freqs:
         c = ops.predict_coh(pack, u, v, w, float(f), tile.freq0,
                             fdelta_ch, tile.tdelta, tile.dec0)
         acc = c if acc is None else acc + c
     return acc / len(freqs)
+
+
+def _all_channels_ok(pack, t):
+    """Whether the all-channels kernels (ops.predict_coh_channels,
+    ops.residuals_multifreq) take this predict: device tensors, no shapelet
+    sources, no beam. SAGECAL_RESIDUAL_LOOP=1 forces the per-channel loop,
+    for A/B runs; SAGECAL_FORCE_REFERENCE=1 implies it."""
+    import os
+    return (t.is_cuda and not getattr(pack, 'shapelets', None)
+            and os.environ.get('SAGECAL_RESIDUAL_LOOP') != '1'
+            and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
+
+
+def _chunk_table(state, T, Nbase, device):
+    """[M, T] int32 on `device`: global chunk id (chunk_off included) of
+    every (cluster, timeslot), the rows of R.chunk_rows_for one per
+    timeslot. Built once per (T, Nbase) and kept next to the layouts."""
+    cache = getattr(state, '_ctab_cache', None)
+    if cache is None:
+        cache = state._ctab_cache = {}
+    key = (T, Nbase, str(device))
+    if key not in cache:
+        rows = []
+        for ci in range(state.M):
+            r = R.chunk_rows_for(ci, state.nchunks, T, 1, T, 'cpu')
+            if r is None:
+                r = torch.zeros(T, dtype=torch.long)
+            rows.append(r + state.chunk_off[ci])
+        cache[key] = torch.stack(rows).to(device=device, dtype=torch.int32)
+    return cache[key]
+
+
+def _subtract_mask(state, skip, device):
+    """[M] bool on `device`, False for the cluster indices of `skip`;
+    remembered per skip set."""
+    cache = getattr(state, '_submask_cache', None)
+    if cache is None:
+        cache = state._submask_cache = {}
+    key = (tuple(sorted(skip)), str(device))
+    if key not in cache:
+        if len(cache) > 8:
+            cache.pop(next(iter(cache)))
+        cache[key] = torch.tensor([ci not in skip for ci in range(state.M)],
+                                  dtype=torch.bool).to(device)
+    return cache[key]
 
 
 def _layout_for(state, bb, T, Nbase, nseg, device):
@@ -450,20 +500,35 @@ def calculate_residuals_multifreq(state, pack, tile, bb, ccid=None, rho=0.0,
     T, Nbase = tile.tilesz, tile.Nbase
     B = tile.x.shape[0]
     fdelta_ch = tile.fdelta / len(tile.freqs)
-    out = torch.empty_like(tile.xo)
     # negative cluster ids: solved during calibration but NOT subtracted
     # from the residual (residual.c:74-75 target-field convention)
     ids = getattr(pack, 'cluster_ids', list(range(state.M)))
     skip = {i for i, c in enumerate(ids) if c < 0}
-    for fi, f in enumerate(tile.freqs):
-        if coh_fn is not None:
-            cohs = coh_fn(float(f)).to(tile.xo.dtype)
-        else:
-            cohs = ops.predict_coh(pack, tile.u, tile.v, tile.w, float(f),
-                                   tile.freq0, fdelta_ch, tile.tdelta,
-                                   tile.dec0)
-        V = total_model(state, cohs, bb, T, Nbase, skip=skip)
-        out[fi] = tile.xo[fi] - V
+    lay = None
+    if coh_fn is None and B == T * Nbase \
+            and _all_channels_ok(pack, tile.u):
+        lay = _layout_for(state, bb, T, Nbase, 1, tile.xo.device)
+    if lay is not None:
+        # predict, apply the solutions and subtract, all channels, in one
+        # launch; no coherency is stored
+        dev = tile.xo.device
+        out = ops.residuals_multifreq(
+            pack, tile.xo, tile.u, tile.v, tile.w, tile.freqs, tile.freq0,
+            fdelta_ch, tile.tdelta, tile.dec0, state.J,
+            _chunk_table(state, T, Nbase, dev), lay.pairs,
+            _subtract_mask(state, skip, dev) if skip else None
+        ).to(tile.xo.dtype)
+    else:
+        out = torch.empty_like(tile.xo)
+        for fi, f in enumerate(tile.freqs):
+            if coh_fn is not None:
+                cohs = coh_fn(float(f)).to(tile.xo.dtype)
+            else:
+                cohs = ops.predict_coh(pack, tile.u, tile.v, tile.w,
+                                       float(f), tile.freq0, fdelta_ch,
+                                       tile.tdelta, tile.dec0)
+            V = total_model(state, cohs, bb, T, Nbase, skip=skip)
+            out[fi] = tile.xo[fi] - V
     if ccid is not None:
         ids = getattr(pack, 'cluster_ids', list(range(state.M)))
         match = [i for i, c in enumerate(ids) if c == ccid]
