@@ -163,19 +163,12 @@ def _beam_config(ms):
     return cfg, t0, z
 
 
-def _channel_gains(pack, tile, cfg, geom, tmjd, freq):
-    """Two-stage station gains [T, K, N] of one channel of the tile. The
-    gains of ALL the tile's channels come from one batched call, made once
-    per tile and kept on it next to the geometry; a frequency that is not
-    one of the tile's channels is evaluated on its own. None for a
-    single-stage config, whose callers compute their gains as before."""
+def _tile_gains(pack, tile, cfg, geom, tmjd):
+    """Station gains [F, T, K, N] of ALL the tile's channels, single- or
+    two-stage: one batched beams.station_beam_gains call, made once per
+    tile and kept on it next to the geometry."""
     from .. import beams
-    if cfg.bf_type != 'tile':
-        return None
     freqs = tuple(float(f) for f in tile.freqs)
-    if float(freq) not in freqs:
-        return beams.station_beam_gains(cfg, geom, [float(freq)],
-                                        tile.u.device)[0]
     # the key names the sources, the times and the channels, not the
     # config: like _beam_geom it relies on one MS giving one config, so
     # tile_enu and the tile pointing cannot change under a tile
@@ -188,7 +181,22 @@ def _channel_gains(pack, tile, cfg, geom, tmjd, freq):
             tile._beam_gains = memo
         except AttributeError:
             pass
-    return memo[1][freqs.index(float(freq))]
+    return memo[1]
+
+
+def _channel_gains(pack, tile, cfg, geom, tmjd, freq):
+    """Two-stage station gains [T, K, N] of one channel of the tile, a row
+    of _tile_gains; a frequency that is not one of the tile's channels is
+    evaluated on its own. None for a single-stage config, whose callers
+    compute their gains as before."""
+    from .. import beams
+    if cfg.bf_type != 'tile':
+        return None
+    freqs = tuple(float(f) for f in tile.freqs)
+    if float(freq) not in freqs:
+        return beams.station_beam_gains(cfg, geom, [float(freq)],
+                                        tile.u.device)[0]
+    return _tile_gains(pack, tile, cfg, geom, tmjd)[freqs.index(float(freq))]
 
 
 def _elem_coeffs(args, z):
@@ -198,18 +206,13 @@ def _elem_coeffs(args, z):
     return None if et == 'synthetic' else et     # name -> LOFAR tables
 
 
-def _channel_ejones(pack, tile, geom, tmjd, freq, coeffs):
-    """Element E-Jones [T, K, 2, 2] of one channel of the tile. Like
-    _channel_gains: the patterns of ALL the tile's channels come from one
+def _tile_ejones(pack, tile, geom, tmjd, coeffs):
+    """Element E-Jones [F, T, K, 2, 2] of ALL the tile's channels: one
     batched evaluation (one kernel launch on the GPU for the LOFAR tables),
-    made once per tile and kept on it; a frequency that is not one of the
-    tile's channels is evaluated on its own. `coeffs` is what _elem_coeffs
-    returns, a table name or None, and is part of the key."""
+    made once per tile and kept on it like _tile_gains. `coeffs` is what
+    _elem_coeffs returns, a table name or None, and is part of the key."""
     from .. import beams
     freqs = tuple(float(f) for f in tile.freqs)
-    if float(freq) not in freqs:
-        return beams.element_jones_channels(coeffs, geom, [float(freq)],
-                                            tile.u.device)[0]
     key = _beam_key(pack, tmjd) + (freqs, coeffs)
     memo = getattr(tile, '_beam_ejones', None)
     if memo is None or memo[0] != key:
@@ -219,7 +222,45 @@ def _channel_ejones(pack, tile, geom, tmjd, freq, coeffs):
             tile._beam_ejones = memo
         except AttributeError:
             pass
-    return memo[1][freqs.index(float(freq))]
+    return memo[1]
+
+
+def _channel_ejones(pack, tile, geom, tmjd, freq, coeffs):
+    """Element E-Jones [T, K, 2, 2] of one channel of the tile, a row of
+    _tile_ejones; a frequency that is not one of the tile's channels is
+    evaluated on its own."""
+    from .. import beams
+    freqs = tuple(float(f) for f in tile.freqs)
+    if float(freq) not in freqs:
+        return beams.element_jones_channels(coeffs, geom, [float(freq)],
+                                            tile.u.device)[0]
+    return _tile_ejones(pack, tile, geom, tmjd,
+                        coeffs)[freqs.index(float(freq))]
+
+
+def _tile_beam(ms, pack, tile, ti, args):
+    """The beam of -B `args.dobeam` at all the tile's channels as the
+    all-channels kernels take it: a dict with 'beam' [F, T, K, N] (modes
+    with the array factor; single-stage configs get theirs from
+    beams.station_beam_gains too) and/or 'ejones' [F, T, K, 2, 2] (modes
+    with the element pattern), from the per-tile memos. None where those
+    kernels do not take the tile (off the GPU, shapelet sources,
+    SAGECAL_RESIDUAL_LOOP=1): the per-channel loop serves it."""
+    from ..solvers import sage
+    if not sage._all_channels_ok(pack, tile.u):
+        return None
+    cfg, t0, z = _beam_config(ms)
+    T = ms.tilesz
+    tmjd = t0 + (ti * T + np.arange(T) + 0.5) * ms.tdelta / 86400.0
+    mode = args.dobeam - 3 if args.dobeam > 3 else args.dobeam
+    geom = _beam_geometry(pack, tile, cfg, tmjd)
+    bm = {}
+    if mode in (1, 2):
+        bm['beam'] = _tile_gains(pack, tile, cfg, geom, tmjd)
+    if mode in (2, 3):
+        bm['ejones'] = _tile_ejones(pack, tile, geom, tmjd,
+                                    _elem_coeffs(args, z))
+    return bm
 
 
 def _predict_with_beam(ms, pack, tile, ti, args):
@@ -247,6 +288,14 @@ def _predict_with_beam(ms, pack, tile, ti, args):
     # channel frequency and average, like the discrete channel model
     mode -= 3
     fdelta_ch = tile.fdelta / len(tile.freqs)
+    bm = _tile_beam(ms, pack, tile, ti, args)
+    if bm is not None:
+        # one launch: every channel with its own beam, summed in the kernel
+        from ..ops import dispatch as ops
+        return ops.predict_coh_channels(
+            pack, tile.u, tile.v, tile.w, tile.freqs, tile.freq0, fdelta_ch,
+            tile.tdelta, tile.dec0, reduce='mean',
+            pairs=ms.bb_tensor()[:ms.Nbase], Nbase=ms.Nbase, **bm)
     acc = None
     for f in tile.freqs:
         gains = _channel_gains(pack, tile, cfg, geom, tmjd, f) \
@@ -340,18 +389,22 @@ def run_calibration(args):
                 nc = state.nchunks[match[0]]
                 Jc = state.J[o:o + nc]
                 state.J[o:o + nc] = Jc / Jc.abs().clamp_min(1e-12)
-        coh_fn = None
+        coh_fn = tile_beam = None
         if args.dobeam:
             # beamed residuals (calculate_residuals_multifreq_withbeam
             # role): per-channel coherencies WITH the station beam, so
-            # the subtracted model matches what was calibrated against
+            # the subtracted model matches what was calibrated against.
+            # The beam of all channels goes to the all-channels kernel
+            # where that takes the tile; coh_fn serves the loop elsewhere
+            # and the -b 1 refinement below
+            tile_beam = _tile_beam(ms, pack, tile, ti, args)
             fdch = tile.fdelta / len(tile.freqs)
             coh_fn = (lambda f, _t=tile, _ti=ti:
                       _predict_channel_with_beam(ms, pack, _t, _ti, args,
                                                  f, fdch))
         xres = sage.calculate_residuals_multifreq(
             state, pack, tile, bb, ccid=ccid, rho=args.rho_corr,
-            coh_fn=coh_fn)
+            coh_fn=coh_fn, beam=tile_beam)
         if args.dochan:
             # per-channel refinement (-b 1, fullbatch_mode.cpp:453-499):
             # polish each channel's solutions with a short joint LBFGS and

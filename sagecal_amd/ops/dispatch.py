@@ -75,21 +75,58 @@ def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0, **kw):
                          **kw)
 
 
+def _beamed_coh_reference(pack, u, v, w, fi, freq, freq0, fdelta, tdelta,
+                          dec0, beam, ejones, pairs, Nbase):
+    """One channel of the beamed all-channels predict off the GPU:
+    beams.predict_coh_withbeam, the fp64 per-source yardstick, with row fi
+    of the given gains [F, T, K, N] and/or patterns [F, T, K, 2, 2] (or
+    [F, T, K, 1, 2, 2]; it knows one pattern per source only)."""
+    from .. import beams
+    if pairs is None:
+        raise ValueError("beam and ejones need the station-pair table "
+                         "`pairs`")
+    Nbase = int(Nbase) or int(pairs.shape[0])
+    T = int(u.shape[0]) // Nbase
+    if ejones is not None and ejones.dim() == 6:
+        if ejones.shape[3] != 1:
+            raise ValueError("per-station E-Jones patterns are applied by "
+                             "the GPU kernels only")
+        ejones = ejones[:, :, :, 0]
+    mode = 3 if beam is None else (1 if ejones is None else 2)
+    bb = pairs[:Nbase].to(device=u.device, dtype=torch.long).repeat(T, 1)
+    # gains and patterns are given, so config, times and geometry are unread
+    return beams.predict_coh_withbeam(
+        pack, u, v, w, freq, freq0, fdelta, tdelta, dec0, None, None, bb,
+        Nbase, T, mode=mode, geom=(), gains=None if beam is None
+        else beam[fi], ejones=None if ejones is None else ejones[fi])
+
+
 def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
-                         reduce=None):
+                         reduce=None, beam=None, ejones=None, pairs=None,
+                         Nbase=0):
     """Coherencies of every channel of `freqs`, [F, M, R, 2, 2], or with
     reduce='mean' their mean over the channels [M, R, 2, 2]; fdelta is the
-    width of one channel. On the GPU one launch of the all-channels kernel
-    (no shapelet sources: ValueError); elsewhere the per-channel loop over
-    the fp64 reference."""
+    width of one channel. Optional station beam per channel: `beam`
+    [F, T, K, N] gains and/or `ejones` [F, T, K, NE, 2, 2] (or
+    [F, T, K, 2, 2]) patterns, with `pairs` [Nbase, 2]. On the GPU one launch
+    of the all-channels kernel (no shapelet sources: ValueError); elsewhere
+    the per-channel loop over the fp64 reference, with a beam over
+    beams.predict_coh_withbeam."""
     if _use_hip(u):
         from . import hip_host
-        return hip_host.predict_coh_channels(pack, u, v, w, freqs, freq0,
-                                             fdelta, tdelta, dec0, reduce)
+        return hip_host.predict_coh_channels(
+            pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0, reduce,
+            beam=beam, ejones=ejones, pairs=pairs, Nbase=Nbase)
     if reduce not in (None, 'mean'):
         raise ValueError(f"reduce must be None or 'mean', got {reduce!r}")
-    cohs = [R.predict_coh(pack, u, v, w, float(f), freq0, fdelta, tdelta,
-                          dec0) for f in freqs]
+    if beam is None and ejones is None:
+        cohs = [R.predict_coh(pack, u, v, w, float(f), freq0, fdelta, tdelta,
+                              dec0) for f in freqs]
+    else:
+        cohs = [_beamed_coh_reference(pack, u, v, w, fi, float(f), freq0,
+                                      fdelta, tdelta, dec0, beam, ejones,
+                                      pairs, Nbase)
+                for fi, f in enumerate(freqs)]
     if not cohs:
         if reduce:
             raise ValueError("the mean over no channels is undefined")
@@ -102,18 +139,21 @@ def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
 
 
 def residuals_multifreq(pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
-                        J, chunk_tab, pairs, subtract=None):
+                        J, chunk_tab, pairs, subtract=None, beam=None,
+                        ejones=None):
     """x[f] - sum over clusters with subtract[ci] of J_p C_f J_q^H,
-    [F, R, 2, 2]. J [Mt, N, 2, 2] packed solutions; chunk_tab [M, T] global
+    [F, R, 2, 2], C_f with the station beam of `beam` [F, T, K, N] and/or
+    `ejones` [F, T, K, NE, 2, 2] (or [F, T, K, 2, 2]) when given. J [Mt, N, 2, 2] packed solutions; chunk_tab [M, T] global
     chunk id per (cluster, timeslot); pairs [Nbase, 2], rows r = t*Nbase + b;
     a row whose pair has a negative entry keeps x. On the GPU one launch of
     the fused kernel (no shapelet sources: ValueError); elsewhere the
-    per-channel loop over R.predict_coh and R.apply_jones."""
+    per-channel loop over R.predict_coh (with a beam,
+    beams.predict_coh_withbeam) and R.apply_jones."""
     if _use_hip(u):
         from . import hip_host
         return hip_host.residuals_multifreq(
             pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0, J,
-            chunk_tab, pairs, subtract)
+            chunk_tab, pairs, subtract, beam=beam, ejones=ejones)
     T, Nbase = int(chunk_tab.shape[1]), int(pairs.shape[0])
     bb = pairs.to(device=x.device, dtype=torch.long).repeat(T, 1)
     ok = (bb >= 0).all(dim=1)
@@ -122,8 +162,13 @@ def residuals_multifreq(pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
                         dtype=torch.long).repeat_interleave(Nbase, dim=1)
     out = torch.empty_like(x)
     for fi, f in enumerate(freqs):
-        cohs = R.predict_coh(pack, u, v, w, float(f), freq0, fdelta, tdelta,
-                             dec0).to(x.dtype)
+        if beam is None and ejones is None:
+            cohs = R.predict_coh(pack, u, v, w, float(f), freq0, fdelta,
+                                 tdelta, dec0).to(x.dtype)
+        else:
+            cohs = _beamed_coh_reference(
+                pack, u, v, w, fi, float(f), freq0, fdelta, tdelta, dec0,
+                beam, ejones, pairs.clamp_min(0), 0).to(x.dtype)
         V = torch.zeros_like(cohs[0])
         for ci in range(cohs.shape[0]):
             if subtract is not None and not bool(subtract[ci]):

@@ -252,10 +252,75 @@ static MfArgs mf_args(
   return a;
 }
 
+// The optional station beam of the two all-channels entry points: beam
+// [F, T, Ke, N] float32, ejones [F, T, Ke, NE, 2, 2] complex64 and pairs
+// [Nbase, 2] int32, checked against the F channels, R rows and K sources of
+// `a`. The kernels index the buffers by channel, timeslot, source and
+// station with no bounds of their own; the caller guarantees pair entries
+// below the station count (negative ones only where the kernel keeps x).
+// Nsta_ej is the station count that ejones goes with (beam brings its own).
+static BeamChannels beam_channels(
+    const c10::optional<torch::Tensor>& beam,
+    const c10::optional<torch::Tensor>& ejones,
+    const c10::optional<torch::Tensor>& pairs, int64_t Nbase,
+    int64_t Nsta_ej, const MfArgs& a, int64_t K, const torch::Tensor& u) {
+  BeamChannels b = {};
+  if (!beam.has_value() && !ejones.has_value()) return b;
+  const int64_t R = a.rows.R, F = a.ch.F;
+  TORCH_CHECK(pairs.has_value() && Nbase > 0,
+              "beam and ejones need the station-pair table and Nbase");
+  TORCH_CHECK(pairs->device() == u.device() &&
+              pairs->scalar_type() == torch::kInt && pairs->is_contiguous() &&
+              pairs->numel() == 2 * Nbase,
+              "pairs must be contiguous [Nbase, 2] int32");
+  TORCH_CHECK(R % Nbase == 0, "rows must be T * Nbase");
+  const int64_t T = R / Nbase;
+  b.pairs = pairs->data_ptr<int>();
+  b.Nbase = (int)Nbase;
+  b.T = (int)T;
+  auto fits = [](int64_t n) { return n >= 1 && n < (int64_t(1) << 31); };
+  if (beam.has_value()) {
+    const torch::Tensor& g = *beam;
+    TORCH_CHECK(g.device() == u.device() &&
+                g.scalar_type() == torch::kFloat && g.is_contiguous() &&
+                g.dim() == 4, "beam must be contiguous [F, T, K, N] float32");
+    TORCH_CHECK(g.size(0) == F && g.size(1) == T,
+                "beam must hold the F channels and T timeslots of the rows");
+    TORCH_CHECK(g.size(2) >= K && fits(g.size(2)) && fits(g.size(3)),
+                "beam covers fewer sources than the pack");
+    b.beam = g.data_ptr<float>();
+    b.Ktot = (int)g.size(2);
+    b.Nsta = (int)g.size(3);
+  }
+  if (ejones.has_value()) {
+    const torch::Tensor& e = *ejones;
+    TORCH_CHECK(e.device() == u.device() &&
+                e.scalar_type() == torch::kComplexFloat &&
+                e.is_contiguous() && e.dim() == 6 && e.size(4) == 2 &&
+                e.size(5) == 2,
+                "ejones must be contiguous [F, T, K, NE, 2, 2] complex64");
+    TORCH_CHECK(e.size(0) == F && e.size(1) == T,
+                "ejones must hold the F channels and T timeslots of the rows");
+    TORCH_CHECK(e.size(2) >= K && fits(e.size(2)),
+                "ejones covers fewer sources than the pack");
+    TORCH_CHECK(fits(Nsta_ej), "ejones needs the station count Nsta");
+    TORCH_CHECK(e.size(3) == 1 || e.size(3) == Nsta_ej,
+                "ejones must hold 1 or Nsta patterns per source");
+    if (beam.has_value())
+      TORCH_CHECK(beam->size(2) == e.size(2) && beam->size(3) == Nsta_ej,
+                  "beam and ejones disagree on K or Nsta");
+    b.ejones = ccptr(e);
+    b.NE = (int)e.size(3);
+    b.Ktot = (int)e.size(2);
+    b.Nsta = (int)Nsta_ej;
+  }
+  return b;
+}
+
 // Coherencies of all F channels in one launch (k_predict_coh_mf):
 // [F, M, R, 4] complex64, or with mean their channel mean [M, R, 4]
-// (k_predict_coh_mean). The caller guarantees that cluster_off is
-// non-decreasing from 0 to K.
+// (k_predict_coh_mean); with beam and/or ejones the _bm / _ej kernels. The
+// caller guarantees that cluster_off is non-decreasing from 0 to K.
 torch::Tensor predict_coh_channels(
     torch::Tensor u, torch::Tensor v, torch::Tensor w,
     torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
@@ -263,14 +328,18 @@ torch::Tensor predict_coh_channels(
     torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
     torch::Tensor sphi, torch::Tensor r1, torch::Tensor stype,
     torch::Tensor cluster_off, torch::Tensor freqs, double fdelta2,
-    double tdelta, bool mean) {
+    double tdelta, bool mean, c10::optional<torch::Tensor> beam,
+    c10::optional<torch::Tensor> ejones, c10::optional<torch::Tensor> pairs,
+    int64_t Nbase, int64_t Nsta_ej) {
   const MfArgs a = mf_args(u, v, w, ll, mm, nn1, flux, eX, eY, eP, cxi, sxi,
                            cphi, sphi, r1, stype, cluster_off, freqs,
                            fdelta2, tdelta);
+  const BeamChannels bm = beam_channels(beam, ejones, pairs, Nbase, Nsta_ej,
+                                        a, ll.size(0), u);
   auto copts = torch::dtype(torch::kComplexFloat).device(u.device());
   auto out = mean ? torch::empty({a.src.M, a.rows.R, 4}, copts)
                   : torch::empty({a.ch.F, a.src.M, a.rows.R, 4}, copts);
-  CHECK_HIP(launch_predict_coh_mf(a.rows, a.src, a.ch, mean ? 1 : 0,
+  CHECK_HIP(launch_predict_coh_mf(a.rows, a.src, a.ch, bm, mean ? 1 : 0,
                                   cptr(out), cur_stream()));
   return out;
 }
@@ -279,7 +348,9 @@ torch::Tensor predict_coh_channels(
 // one launch (k_residual_mf): x [F, R, 4] complex64, J [Mt, N, 4]
 // complex64, chunk_tab [M, T] int32 global chunk ids, pairs [Nbase, 2]
 // int32, R == T * Nbase, skip [M] int32 or none. Returns [F, R, 4]. The
-// caller guarantees chunk ids below Mt and pair entries below N.
+// caller guarantees chunk ids below Mt and pair entries below N. With beam
+// [F, T, Ke, Nsta] and/or ejones [F, T, Ke, NE, 2, 2] the coherencies carry
+// the station beam (k_residual_mf_bm / _ej), indexed through the same pairs.
 torch::Tensor residuals_multifreq(
     torch::Tensor x, torch::Tensor u, torch::Tensor v, torch::Tensor w,
     torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
@@ -288,7 +359,9 @@ torch::Tensor residuals_multifreq(
     torch::Tensor sphi, torch::Tensor r1, torch::Tensor stype,
     torch::Tensor cluster_off, torch::Tensor freqs, double fdelta2,
     double tdelta, torch::Tensor J, torch::Tensor chunk_tab,
-    torch::Tensor pairs, c10::optional<torch::Tensor> skip) {
+    torch::Tensor pairs, c10::optional<torch::Tensor> skip,
+    c10::optional<torch::Tensor> beam, c10::optional<torch::Tensor> ejones,
+    int64_t Nsta_ej) {
   const MfArgs a = mf_args(u, v, w, ll, mm, nn1, flux, eX, eY, eP, cxi, sxi,
                            cphi, sphi, r1, stype, cluster_off, freqs,
                            fdelta2, tdelta);
@@ -324,9 +397,11 @@ torch::Tensor residuals_multifreq(
   res.Nbase = (int)pairs.size(0);
   res.T = (int)chunk_tab.size(1);
   res.N = (int)J.size(1);
+  const BeamChannels bm = beam_channels(beam, ejones, pairs, pairs.size(0),
+                                        Nsta_ej, a, ll.size(0), u);
   auto out = torch::empty({F, R, 4},
       torch::dtype(torch::kComplexFloat).device(u.device()));
-  CHECK_HIP(launch_residual_mf(a.rows, a.src, a.ch, res, cptr(out),
+  CHECK_HIP(launch_residual_mf(a.rows, a.src, a.ch, bm, res, cptr(out),
                                cur_stream()));
   return out;
 }
@@ -626,7 +701,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eY"), py::arg("eP"), py::arg("cxi"), py::arg("sxi"),
         py::arg("cphi"), py::arg("sphi"), py::arg("r1"), py::arg("stype"),
         py::arg("cluster_off"), py::arg("freqs"), py::arg("fdelta2"),
-        py::arg("tdelta"), py::arg("mean") = false);
+        py::arg("tdelta"), py::arg("mean") = false,
+        py::arg("beam") = py::none(), py::arg("ejones") = py::none(),
+        py::arg("pairs") = py::none(), py::arg("Nbase") = 0,
+        py::arg("Nsta") = 0);
   m.def("residuals_multifreq", &residuals_multifreq,
         "predict and subtract, all channels in one launch (gfx950)",
         py::arg("x"), py::arg("u"), py::arg("v"), py::arg("w"), py::arg("ll"),
@@ -635,8 +713,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cphi"), py::arg("sphi"), py::arg("r1"), py::arg("stype"),
         py::arg("cluster_off"), py::arg("freqs"), py::arg("fdelta2"),
         py::arg("tdelta"), py::arg("J"), py::arg("chunk_tab"),
-        py::arg("pairs"), py::arg("skip") = py::none());
+        py::arg("pairs"), py::arg("skip") = py::none(),
+        py::arg("beam") = py::none(), py::arg("ejones") = py::none(),
+        py::arg("Nsta") = 0);
   m.attr("PREDICT_MF_NF") = PREDICT_MF_NF;
+  m.attr("PREDICT_MF_NF_EJ") = PREDICT_MF_NF_EJ;
   m.def("array_beam_gains", &array_beam_gains,
         "station array-factor gains [T, K, N] (gfx950)", py::arg("elem"),
         py::arg("nelem"), py::arg("du"), py::arg("below"), py::arg("kf"));

@@ -82,6 +82,19 @@ struct BeamArgs {
   int NE;
 };
 
+// Station beam of the all-channels kernels (predict_mf.hip), the buffers of
+// BeamArgs with a leading channel axis: channel f reads row f. beam and
+// ejones both null: the kernels without beam run. beam alone: the scalar
+// gain kernels (_bm). ejones, with or without beam: the E-Jones kernels
+// (_ej). pairs, Nbase, T and Ktot are read with either, and the rows are
+// R == T * Nbase; Nsta strides beam, NE (1 or Nsta) strides ejones.
+struct BeamChannels {
+  const float* beam;        // [F, T, Ktot, Nsta] or null
+  const float2* ejones;     // [F, T, Ktot, NE, 2, 2] or null
+  const int* pairs;         // [Nbase, 2]
+  int Nbase, T, Ktot, Nsta, NE;
+};
+
 extern "C" {
 
 // out [M, R, 4]: written by launch_predict_coh, added into by
@@ -92,20 +105,28 @@ hipError_t launch_predict_coh(RowsUVW rows, SourceArrays src, Channel ch,
 hipError_t launch_shapelet_coh(RowsUVW rows, ShapeletTab tab, Channel ch,
                                BeamArgs bm, float2* out, hipStream_t stream);
 
-// All channels in one launch, no beam and no shapelet sources (their
-// fluxes arrive zeroed). Channels a thread carries per pass:
+// All channels in one launch, no shapelet sources (their fluxes arrive
+// zeroed), with the station beam of bm when it holds one. Channels a thread
+// carries per pass, without E-Jones and with:
 #ifndef PREDICT_MF_NF
 #define PREDICT_MF_NF 2
 #endif
+#ifndef PREDICT_MF_NF_EJ
+#define PREDICT_MF_NF_EJ 1
+#endif
 // out [F, M, R, 4], or with mean != 0 the channel mean [M, R, 4].
-// hipErrorInvalidValue: F < 1 or R < 1.
+// hipErrorInvalidValue: F < 1 or R < 1; with a beam or E-Jones: no pairs or
+// Nbase, R != T * Nbase, Ktot or Nsta < 1, or (E-Jones) NE neither 1 nor
+// Nsta.
 hipError_t launch_predict_coh_mf(RowsUVW rows, SourceArrays src, Channels ch,
-                                 int mean, float2* out, hipStream_t stream);
+                                 BeamChannels bm, int mean, float2* out,
+                                 hipStream_t stream);
 // out [F, R, 4] = x - sum over clusters with skip == 0 of J_p C J_q^H.
 // hipErrorInvalidValue: F < 1, R < 1, R != T * Nbase, or x, J, chunk_tab
-// or pairs missing.
+// or pairs missing; with a beam or E-Jones what launch_predict_coh_mf
+// refuses, or a bm that disagrees with res on pairs, Nbase or T.
 hipError_t launch_residual_mf(RowsUVW rows, SourceArrays src, Channels ch,
-                              ResidualArgs res, float2* out,
+                              BeamChannels bm, ResidualArgs res, float2* out,
                               hipStream_t stream);
 
 hipError_t launch_array_beam(

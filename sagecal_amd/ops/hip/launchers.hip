@@ -41,37 +41,70 @@ hipError_t launch_shapelet_coh(RowsUVW rows, ShapeletTab tab, Channel ch,
                      out, stream);
 }
 
-// blocks of 128 rows; passes of MF_NF channels along grid z except for the
+// blocks of 128 rows; passes of nf channels along grid z except for the
 // mean, whose threads walk the passes themselves
-static bool mf_grid(int R, int F, bool z_passes, dim3* grid) {
+static bool mf_grid(int R, int F, int nf, bool z_passes, dim3* grid) {
   if (F < 1 || R < 1) return false;
-  const long long gz = z_passes ? (F + MF_NF - 1) / MF_NF : 1;
+  const long long gz = z_passes ? (F + nf - 1) / nf : 1;
   if (gz > 65535) return false;
   *grid = dim3((R + 127) / 128, 1, (unsigned)gz);
   return true;
 }
 
+// MF_PLAIN, MF_GAIN or MF_EJ for the buffers of bm, or -1 when the kernels
+// would index them out of bounds
+static int mf_beam_mode(const BeamChannels& bm, int R) {
+  if (bm.beam == nullptr && bm.ejones == nullptr) return MF_PLAIN;
+  if (bm.pairs == nullptr || bm.Nbase < 1 || bm.T < 1 || bm.Ktot < 1 ||
+      bm.Nsta < 1 || (long long)bm.T * bm.Nbase != R)
+    return -1;
+  if (bm.ejones == nullptr) return MF_GAIN;
+  return bm.NE == 1 || bm.NE == bm.Nsta ? MF_EJ : -1;
+}
+
 hipError_t launch_predict_coh_mf(RowsUVW rows, SourceArrays src, Channels ch,
-                                 int mean, float2* out, hipStream_t stream) {
+                                 BeamChannels bm, int mean, float2* out,
+                                 hipStream_t stream) {
   dim3 grid;
-  if (!mf_grid(rows.R, ch.F, !mean, &grid) || ch.freqs == nullptr)
+  const int mode = mf_beam_mode(bm, rows.R);
+  if (mode < 0 || ch.freqs == nullptr ||
+      !mf_grid(rows.R, ch.F, mode == MF_EJ ? MF_NF_EJ : MF_NF, !mean, &grid))
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(mean ? k_predict_coh_mean : k_predict_coh_mf, grid,
-                     dim3(128), 0, stream, rows, src, ch, out);
+  if (mode == MF_PLAIN)
+    hipLaunchKernelGGL(mean ? k_predict_coh_mean : k_predict_coh_mf, grid,
+                       dim3(128), 0, stream, rows, src, ch, out);
+  else if (mode == MF_GAIN)
+    hipLaunchKernelGGL(mean ? k_predict_coh_mean_bm : k_predict_coh_mf_bm,
+                       grid, dim3(128), 0, stream, rows, src, ch, bm, out);
+  else
+    hipLaunchKernelGGL(mean ? k_predict_coh_mean_ej : k_predict_coh_mf_ej,
+                       grid, dim3(128), 0, stream, rows, src, ch, bm, out);
   return hipGetLastError();
 }
 
 hipError_t launch_residual_mf(RowsUVW rows, SourceArrays src, Channels ch,
-                              ResidualArgs res, float2* out,
+                              BeamChannels bm, ResidualArgs res, float2* out,
                               hipStream_t stream) {
   dim3 grid;
-  if (!mf_grid(rows.R, ch.F, true, &grid) || ch.freqs == nullptr ||
+  const int mode = mf_beam_mode(bm, rows.R);
+  if (mode < 0 || ch.freqs == nullptr ||
+      !mf_grid(rows.R, ch.F, mode == MF_EJ ? MF_NF_EJ : MF_NF, true, &grid) ||
       res.x == nullptr || res.J == nullptr || res.chunk_tab == nullptr ||
       res.pairs == nullptr || res.Nbase < 1 || res.T < 1 || res.N < 1 ||
       (long long)res.T * res.Nbase != rows.R)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_residual_mf, grid, dim3(128), 0, stream, rows, src,
-                     ch, res, out);
+  if (mode != MF_PLAIN && (bm.pairs != res.pairs || bm.Nbase != res.Nbase ||
+                           bm.T != res.T))
+    return hipErrorInvalidValue;
+  if (mode == MF_PLAIN)
+    hipLaunchKernelGGL(k_residual_mf, grid, dim3(128), 0, stream, rows, src,
+                       ch, res, out);
+  else if (mode == MF_GAIN)
+    hipLaunchKernelGGL(k_residual_mf_bm, grid, dim3(128), 0, stream, rows,
+                       src, ch, bm, res, out);
+  else
+    hipLaunchKernelGGL(k_residual_mf_ej, grid, dim3(128), 0, stream, rows,
+                       src, ch, bm, res, out);
   return hipGetLastError();
 }
 

@@ -463,18 +463,103 @@ def _mf_pack(pack, device, what):
     return gp
 
 
+def _check_beam_channels(beam, ejones, pairs, Nbase, F, R, K, dev,
+                         negative_ok=False, Nsta=None):
+    """Host-side contract of the beamed all-channels kernels, which index
+    beam [F, T, Ke, N] and ejones [F, T, Ke, NE, 2, 2] (or [F, T, Ke, 2, 2],
+    one pattern, NE = 1) by channel, timeslot, source and station with no
+    checks of their own. Checked once here, as _check_ejones does for one
+    channel: leading dimension F, [T, Ke] agreement, Ke >= K, the station
+    range of `pairs` inside N, NE in (1, N). negative_ok: the residual
+    kernels keep x on a row with a negative pair entry and look nothing up
+    for it, the predict kernels have no such row. Nsta: the station count
+    when the caller has one (J's), else beam's, else NE or the largest pair
+    entry + 1. Returns the keyword arguments of the extension: beam
+    float32, ejones complex64 six-dimensional, pairs int32 [Nbase, 2], all
+    contiguous on `dev`, Nbase and Nsta."""
+    if pairs is None:
+        raise ValueError("beam and ejones need the station-pair table "
+                         "`pairs`")
+    Nbase = int(Nbase) or int(pairs.shape[0])
+    if pairs.dim() != 2 or pairs.shape[0] < Nbase or pairs.shape[1] != 2 \
+            or Nbase < 1:
+        raise ValueError("pairs must be [Nbase, 2]")
+    if R % Nbase:
+        raise ValueError(f"{R} rows are no whole timeslots of {Nbase} "
+                         "baselines")
+    T = R // Nbase
+    # the range is remembered per tensor object: ask for the caller's own
+    # table where all of it is read
+    lo, hi = _pair_range(pairs if pairs.shape[0] == Nbase
+                         else pairs[:Nbase])
+    pairs = pairs[:Nbase].to(device=dev, dtype=torch.int32).contiguous()
+    N = Nsta
+    kw = {}
+    if beam is not None:
+        if beam.dim() != 4:
+            raise ValueError("beam must be [F, T, K, N], got "
+                             f"{tuple(beam.shape)}")
+        if N is None:
+            N = int(beam.shape[3])
+        if tuple(beam.shape[:2]) != (F, T) or int(beam.shape[3]) != N:
+            raise ValueError(f"beam must be [{F}, {T}, K, {N}], got "
+                             f"{tuple(beam.shape)}")
+        if beam.shape[2] < K:
+            raise ValueError(f"beam covers {beam.shape[2]} sources, the "
+                             f"pack has {K}")
+        kw['beam'] = beam.to(device=dev, dtype=torch.float32).contiguous()
+    if ejones is not None:
+        if ejones.dim() == 5:                # [F, T, K, 2, 2]: one pattern
+            ejones = ejones.unsqueeze(3)
+        if ejones.dim() != 6 or tuple(ejones.shape[4:]) != (2, 2):
+            raise ValueError("ejones must be [F, T, K, NE, 2, 2] or "
+                             f"[F, T, K, 2, 2], got {tuple(ejones.shape)}")
+        Ke, NE = int(ejones.shape[2]), int(ejones.shape[3])
+        if tuple(ejones.shape[:2]) != (F, T):
+            raise ValueError(f"ejones must be [{F}, {T}, K, NE, 2, 2], got "
+                             f"{tuple(ejones.shape)}")
+        if Ke < K:
+            raise ValueError(f"ejones covers {Ke} sources, the pack has {K}")
+        if beam is not None and int(beam.shape[2]) != Ke:
+            raise ValueError("beam and ejones disagree on [T, K]")
+        if N is None:
+            N = NE if NE != 1 else hi + 1
+        if NE not in (1, N):
+            raise ValueError(f"ejones holds {NE} patterns per source; must "
+                             f"be 1 or the station count {N}")
+        kw['ejones'] = ejones.to(device=dev,
+                                 dtype=torch.complex64).contiguous()
+    if hi >= N or (lo < 0 and not negative_ok):
+        raise ValueError(f"pairs name stations {lo}..{hi}, outside the "
+                         f"{N} stations of the beam buffers")
+    return dict(kw, pairs=pairs, Nbase=Nbase, Nsta=N)
+
+
 def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
-                         reduce=None):
+                         reduce=None, beam=None, ejones=None, pairs=None,
+                         Nbase=0):
     """Coherencies of every channel of `freqs` in one launch
     (k_predict_coh_mf): [F, M, R, 2, 2] complex64, channel f equal to
-    predict_coh at freqs[f] without beam (bit for bit on point sources; an
-    extended source's envelope may round differently). reduce='mean' returns
-    their mean over the channels [M, R, 2, 2] instead (k_predict_coh_mean)
-    and never stores the channels; it needs at least one. fdelta is the
-    width of one channel. No station beam, no E-Jones; a pack with shapelet
-    sources raises ValueError. Empty freqs or no rows return an empty tensor
-    without a launch. Once the pack and the flux stack of this frequency
-    tuple are on the device the path has no host synchronisation."""
+    predict_coh at freqs[f] (bit for bit on point sources; an extended
+    source's envelope may round differently). reduce='mean' returns their
+    mean over the channels [M, R, 2, 2] instead (k_predict_coh_mean) and
+    never stores the channels; it needs at least one. fdelta is the width
+    of one channel.
+
+    Optional station beam, per channel: `beam` [F, T, K, N] real gains
+    (beams.station_beam_gains) and/or `ejones` [F, T, K, NE, 2, 2] complex
+    patterns, NE = 1 or N, or [F, T, K, 2, 2] (what
+    beams.element_jones_channels returns) for NE = 1, with `pairs`
+    [Nbase, 2] and rows r = t * Nbase + b. Channel f is then predict_coh at
+    freqs[f] with beam[f] and ejones[f]: the _bm kernels with gains alone,
+    the _ej kernels with patterns. With neither the call is what it was
+    without these arguments.
+
+    A pack with shapelet sources raises ValueError. Empty freqs or no rows
+    return an empty tensor without a launch. Once the pack and the flux
+    stack of this frequency tuple are on the device, and after the first
+    call with a new pair table (whose index range is read back), the path
+    has no host synchronisation."""
     if reduce not in (None, 'mean'):
         raise ValueError(f"reduce must be None or 'mean', got {reduce!r}")
     gp = _mf_pack(pack, u.device, 'predict_coh_channels')
@@ -485,23 +570,30 @@ def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
     if F == 0 or R == 0:
         shape = (gp.M, R, 2, 2) if reduce else (F, gp.M, R, 2, 2)
         return torch.empty(shape, dtype=torch.complex64, device=u.device)
+    bm = {}
+    if beam is not None or ejones is not None:
+        bm = _check_beam_channels(beam, ejones, pairs, Nbase, F, R, gp.K,
+                                  u.device)
     out = _ext().predict_coh_channels(
         *_mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0),
-        mean=reduce == 'mean')
+        mean=reduce == 'mean', **bm)
     return out.view(*out.shape[:-1], 2, 2)
 
 
 def residuals_multifreq(pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
-                        J, chunk_tab, pairs, subtract=None):
+                        J, chunk_tab, pairs, subtract=None, beam=None,
+                        ejones=None):
     """x[f] - sum over subtracted clusters of J_p C_f J_q^H for every
     channel in one launch (k_residual_mf); the coherencies C_f are those of
-    predict_coh_channels and are never stored. x [F, R, 2, 2] complex; J
+    predict_coh_channels, with the station beam of `beam` [F, T, K, N]
+    and/or `ejones` [F, T, K, NE, 2, 2] or [F, T, K, 2, 2] when given
+    (k_residual_mf_bm / _ej; N is J's station count), and are never stored. x [F, R, 2, 2] complex; J
     [Mt, N, 2, 2] packed solutions; chunk_tab [M, T] global chunk id of each
     (cluster, timeslot), chunk_off[ci] included; pairs [Nbase, 2] stations
     of the baselines, R = T * Nbase; subtract [M] booleans, False for a
     cluster that is solved but stays in the residual (negative cluster id,
     residual.c:74), default all True. A row whose pair has a negative entry
-    keeps x. Returns [F, R, 2, 2] complex64. The first call with a new pair
+    keeps x and looks up no beam. Returns [F, R, 2, 2] complex64. The first call with a new pair
     or chunk table reads its index range back for the bounds check; after
     that, and once pack and flux stack are on the device, the path has no
     host synchronisation."""
@@ -535,11 +627,16 @@ def residuals_multifreq(pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
         if tuple(sub.shape) != (gp.M,):
             raise ValueError(f"subtract must be [{gp.M}]")
         skip = (~sub).to(device=dev, dtype=torch.int32).contiguous()
+    bm = {}
+    if beam is not None or ejones is not None:
+        bm = _check_beam_channels(beam, ejones, pairs, 0, F, R, gp.K, dev,
+                                  negative_ok=True, Nsta=N)
+        bm = {k: bm[k] for k in ('beam', 'ejones', 'Nsta') if k in bm}
     out = _ext().residuals_multifreq(
         x.to(torch.complex64).reshape(F, R, 4).contiguous(),
         *_mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0),
         J.to(torch.complex64).reshape(Mt, N, 4).contiguous(), chunk_tab,
-        pairs, skip)
+        pairs, skip, **bm)
     return out.view(F, R, 2, 2)
 
 

@@ -137,8 +137,8 @@ def precalc_coherencies(pack, tile, device=None, discrete=True):
 def _all_channels_ok(pack, t):
     """Whether the all-channels kernels (ops.predict_coh_channels,
     ops.residuals_multifreq) take this predict: device tensors, no shapelet
-    sources, no beam. SAGECAL_RESIDUAL_LOOP=1 forces the per-channel loop,
-    for A/B runs; SAGECAL_FORCE_REFERENCE=1 implies it."""
+    sources. SAGECAL_RESIDUAL_LOOP=1 forces the per-channel loop, for A/B
+    runs; SAGECAL_FORCE_REFERENCE=1 implies it."""
     import os
     return (t.is_cuda and not getattr(pack, 'shapelets', None)
             and os.environ.get('SAGECAL_RESIDUAL_LOOP') != '1'
@@ -486,7 +486,7 @@ def sagefit(state, cohs, tile, bb, opts, flags=None, admm_terms=None):
 
 
 def calculate_residuals_multifreq(state, pack, tile, bb, ccid=None, rho=0.0,
-                                  device=None, coh_fn=None):
+                                  device=None, coh_fn=None, beam=None):
     """Per-channel residuals with the solved gains
     (residual.c calculate_residuals_multifreq:940): re-predict each channel's
     coherencies at its own frequency (spectral-index flux scaling + per
@@ -496,7 +496,14 @@ def calculate_residuals_multifreq(state, pack, tile, bb, ccid=None, rho=0.0,
     (mat_invert(J + rho I), residual.c:125-196). coh_fn(freq) overrides
     the per-channel coherency predict — the beamed-residual hook
     (calculate_residuals_multifreq_withbeam, Dirac_radio.h:495-497).
-    Returns xres [F, B, 2, 2]."""
+
+    beam: the station beam of all the tile's channels, a dict with 'beam'
+    [F, T, K, N] gains and/or 'ejones' [F, T, K, NE, 2, 2] (or
+    [F, T, K, 2, 2]) patterns, the arguments of ops.residuals_multifreq.
+    Where the all-channels kernel takes the tile (_all_channels_ok and whole
+    timeslots) the beamed residuals are its one launch; elsewhere the
+    coh_fn loop runs, so a caller with a beam gives both. coh_fn alone
+    always takes the loop. Returns xres [F, B, 2, 2]."""
     T, Nbase = tile.tilesz, tile.Nbase
     B = tile.x.shape[0]
     fdelta_ch = tile.fdelta / len(tile.freqs)
@@ -505,9 +512,15 @@ def calculate_residuals_multifreq(state, pack, tile, bb, ccid=None, rho=0.0,
     ids = getattr(pack, 'cluster_ids', list(range(state.M)))
     skip = {i for i, c in enumerate(ids) if c < 0}
     lay = None
-    if coh_fn is None and B == T * Nbase \
+    if beam is not None and not (beam.get('beam') is not None
+                                 or beam.get('ejones') is not None):
+        beam = None
+    if (coh_fn is None or beam is not None) and B == T * Nbase \
             and _all_channels_ok(pack, tile.u):
         lay = _layout_for(state, bb, T, Nbase, 1, tile.xo.device)
+    if lay is None and beam is not None and coh_fn is None:
+        raise ValueError("a beam that the all-channels kernel cannot take "
+                         "needs coh_fn for the per-channel loop")
     if lay is not None:
         # predict, apply the solutions and subtract, all channels, in one
         # launch; no coherency is stored
@@ -516,8 +529,8 @@ def calculate_residuals_multifreq(state, pack, tile, bb, ccid=None, rho=0.0,
             pack, tile.xo, tile.u, tile.v, tile.w, tile.freqs, tile.freq0,
             fdelta_ch, tile.tdelta, tile.dec0, state.J,
             _chunk_table(state, T, Nbase, dev), lay.pairs,
-            _subtract_mask(state, skip, dev) if skip else None
-        ).to(tile.xo.dtype)
+            _subtract_mask(state, skip, dev) if skip else None,
+            **(beam or {})).to(tile.xo.dtype)
     else:
         out = torch.empty_like(tile.xo)
         for fi, f in enumerate(tile.freqs):

@@ -15,6 +15,16 @@ between the two paths' outputs. Needs a GPU.
 
     python tools/bench_residual_predict.py --out result.json [--runs N]
 
+--beam MODE (1: station gains, 2: gains and element patterns, 3: patterns
+alone; the -B 1/4, 2/5 and 3/6 of the command line) times the beamed paths
+on the same workload instead: random gains [F, T, K, N] in [0.2, 1] and
+random patterns [F, T, K, 2, 2] (one per source, NE = 1), given to
+calculate_residuals_multifreq as beam= together with the coh_fn of the
+per-channel loop, and the wideband solve model of -B 4/5/6, the channel
+mean of the beamed predicts: one predict_coh_channels(reduce='mean') call
+against the loop over predict_coh. The loop is what runs without the
+all-channels kernels, selected by the same switch.
+
 Kernel durations come from a second run under the profiler, which slows
 the host and so gets no timings of its own:
 
@@ -65,10 +75,57 @@ def merge_kernels(out, stats_csv):
         json.dump(res, f, indent=1)
 
 
+def beamed_functions(mode, sage, state, pack, tile, bb):
+    """The two timed functions with the beam of `mode`, each taking the
+    all-channels kernel or the per-channel loop by the switch."""
+    import torch
+    from sagecal_amd.ops import dispatch as ops
+    from sagecal_amd.ops import hip_host
+    dev = tile.u.device
+    F, N, Nbase = len(tile.freqs), SHAPE['stations'], tile.Nbase
+    T, K = tile.tilesz, int(pack.cluster_off[-1])
+    g = torch.Generator().manual_seed(11)
+    bm = {}
+    if mode in (1, 2):
+        bm['beam'] = (0.2 + 0.8 * torch.rand(F, T, K, N, generator=g)).to(dev)
+    if mode in (2, 3):
+        bm['ejones'] = torch.view_as_complex(
+            2.0 * torch.rand(F, T, K, 2, 2, 2, generator=g) - 1.0).to(dev)
+    pairs = bb[:Nbase].to(torch.int32).contiguous()
+    freqs = [float(f) for f in tile.freqs]
+    fdch = tile.fdelta / F
+
+    def coh_fn(f):
+        fi = freqs.index(f)
+        return hip_host.predict_coh(
+            pack, tile.u, tile.v, tile.w, f, tile.freq0, fdch, tile.tdelta,
+            tile.dec0, pairs=pairs, Nbase=Nbase,
+            beam=bm['beam'][fi] if 'beam' in bm else None,
+            ejones=bm['ejones'][fi].unsqueeze(2) if 'ejones' in bm else None)
+
+    def mean_predict():
+        if sage._all_channels_ok(pack, tile.u):
+            return ops.predict_coh_channels(
+                pack, tile.u, tile.v, tile.w, freqs, tile.freq0, fdch,
+                tile.tdelta, tile.dec0, reduce='mean', pairs=pairs,
+                Nbase=Nbase, **bm)
+        acc = None
+        for f in freqs:
+            c = coh_fn(f)
+            acc = c if acc is None else acc + c
+        return acc / F
+
+    return {'calculate_residuals_multifreq':
+            lambda: sage.calculate_residuals_multifreq(
+                state, pack, tile, bb, coh_fn=coh_fn, beam=bm),
+            'wideband_mean_predict': mean_predict}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('--out', help='result JSON path')
     ap.add_argument('--runs', type=int, default=10)
+    ap.add_argument('--beam', type=int, choices=(1, 2, 3), metavar='MODE')
     ap.add_argument('--profile-run', action='store_true')
     ap.add_argument('--merge-kernels', metavar='CSV')
     args = ap.parse_args()
@@ -104,6 +161,8 @@ def main():
            lambda: sage.calculate_residuals_multifreq(state, pack, tile, bb),
            'precalc_coherencies':
            lambda: sage.precalc_coherencies(pack, tile)}
+    if args.beam:
+        fns = beamed_functions(args.beam, sage, state, pack, tile, bb)
     paths = (('fused', False), ('loop', True))
 
     if args.profile_run:
@@ -118,6 +177,7 @@ def main():
            'rows': int(tile.u.shape[0]), 'channels': len(tile.freqs),
            'clusters': pack.M, 'sources': int(pack.cluster_off[-1]),
            'chunks': state.Mt, 'warmup': WARMUP, 'runs': args.runs,
+           'beam_mode': args.beam,
            'order': 'fused, loop, fused, loop, ...', 'functions': {}}
     for name, fn in fns.items():
         rec = {p: {'ms_per_call': []} for p, _ in paths}
