@@ -294,7 +294,7 @@ def _predict_with_beam(ms, pack, tile, ti, args):
         from ..ops import dispatch as ops
         return ops.predict_coh_channels(
             pack, tile.u, tile.v, tile.w, tile.freqs, tile.freq0, fdelta_ch,
-            tile.tdelta, tile.dec0, reduce='mean',
+            tile.tdelta, tile.dec0, reduce='mean', shapelets=True,
             pairs=ms.bb_tensor()[:ms.Nbase], Nbase=ms.Nbase, **bm)
     acc = None
     for f in tile.freqs:

@@ -103,20 +103,23 @@ def _beamed_coh_reference(pack, u, v, w, fi, freq, freq0, fdelta, tdelta,
 
 def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
                          reduce=None, beam=None, ejones=None, pairs=None,
-                         Nbase=0):
+                         Nbase=0, shapelets=False):
     """Coherencies of every channel of `freqs`, [F, M, R, 2, 2], or with
     reduce='mean' their mean over the channels [M, R, 2, 2]; fdelta is the
     width of one channel. Optional station beam per channel: `beam`
     [F, T, K, N] gains and/or `ejones` [F, T, K, NE, 2, 2] (or
     [F, T, K, 2, 2]) patterns, with `pairs` [Nbase, 2]. On the GPU one launch
-    of the all-channels kernel (no shapelet sources: ValueError); elsewhere
+    of the all-channels kernel, and with shapelets=True a second one for the
+    pack's shapelet sources (without it they raise ValueError); elsewhere
     the per-channel loop over the fp64 reference, with a beam over
-    beams.predict_coh_withbeam."""
+    beams.predict_coh_withbeam, which takes shapelet sources as they are
+    and ignores `shapelets`."""
     if _use_hip(u):
         from . import hip_host
         return hip_host.predict_coh_channels(
             pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0, reduce,
-            beam=beam, ejones=ejones, pairs=pairs, Nbase=Nbase)
+            beam=beam, ejones=ejones, pairs=pairs, Nbase=Nbase,
+            shapelets=shapelets)
     if reduce not in (None, 'mean'):
         raise ValueError(f"reduce must be None or 'mean', got {reduce!r}")
     if beam is None and ejones is None:
@@ -140,20 +143,23 @@ def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
 
 def residuals_multifreq(pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
                         J, chunk_tab, pairs, subtract=None, beam=None,
-                        ejones=None):
+                        ejones=None, shapelets=False):
     """x[f] - sum over clusters with subtract[ci] of J_p C_f J_q^H,
     [F, R, 2, 2], C_f with the station beam of `beam` [F, T, K, N] and/or
     `ejones` [F, T, K, NE, 2, 2] (or [F, T, K, 2, 2]) when given. J [Mt, N, 2, 2] packed solutions; chunk_tab [M, T] global
     chunk id per (cluster, timeslot); pairs [Nbase, 2], rows r = t*Nbase + b;
     a row whose pair has a negative entry keeps x. On the GPU one launch of
-    the fused kernel (no shapelet sources: ValueError); elsewhere the
+    the fused kernel, and with shapelets=True a second one for the pack's
+    shapelet sources (without it they raise ValueError); elsewhere the
     per-channel loop over R.predict_coh (with a beam,
-    beams.predict_coh_withbeam) and R.apply_jones."""
+    beams.predict_coh_withbeam) and R.apply_jones, which ignores
+    `shapelets`."""
     if _use_hip(u):
         from . import hip_host
         return hip_host.residuals_multifreq(
             pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0, J,
-            chunk_tab, pairs, subtract, beam=beam, ejones=ejones)
+            chunk_tab, pairs, subtract, beam=beam, ejones=ejones,
+            shapelets=shapelets)
     T, Nbase = int(chunk_tab.shape[1]), int(pairs.shape[0])
     bb = pairs.to(device=x.device, dtype=torch.long).repeat(T, 1)
     ok = (bb >= 0).all(dim=1)

@@ -113,6 +113,70 @@ torch::Tensor predict_coh(
   return out;
 }
 
+// The mode table of hip_host.ShapeletTable, checked against the device of
+// u and its S = src.size(0) entries; flux and r1 are left to the caller.
+static ShapeletTab shapelet_tab(
+    const torch::Tensor& u, const torch::Tensor& src,
+    const torch::Tensor& cluster, const torch::Tensor& n0,
+    const torch::Tensor& beta, const torch::Tensor& off,
+    const torch::Tensor& coef, const torch::Tensor& cxi,
+    const torch::Tensor& sxi, const torch::Tensor& cphi,
+    const torch::Tensor& sphi, const torch::Tensor& psign,
+    const torch::Tensor& a, const torch::Tensor& b, const torch::Tensor& ceP,
+    const torch::Tensor& seP, const torch::Tensor& ll,
+    const torch::Tensor& mm, const torch::Tensor& nn1,
+    const torch::Tensor& rec) {
+  const int64_t S = src.size(0);
+  auto chk = [&](const torch::Tensor& t, torch::ScalarType ty, int64_t n,
+                 const char* name) {
+    TORCH_CHECK(t.device() == u.device(), name, " is on another device");
+    TORCH_CHECK(t.scalar_type() == ty, name, " has the wrong dtype");
+    TORCH_CHECK(t.is_contiguous() && t.numel() == n, name,
+                " must be contiguous with ", n, " elements");
+  };
+  chk(src, torch::kInt, S, "src");
+  chk(cluster, torch::kInt, S, "cluster");
+  chk(n0, torch::kInt, S, "n0");
+  chk(beta, torch::kFloat, S, "beta");
+  chk(off, torch::kInt, S + 1, "off");
+  TORCH_CHECK(coef.scalar_type() == torch::kFloat && coef.is_contiguous() &&
+              coef.device() == u.device(), "coef must be contiguous float32");
+  chk(cxi, torch::kFloat, S, "cxi");
+  chk(sxi, torch::kFloat, S, "sxi");
+  chk(cphi, torch::kFloat, S, "cphi");
+  chk(sphi, torch::kFloat, S, "sphi");
+  chk(psign, torch::kFloat, S, "psign");
+  chk(a, torch::kFloat, S, "a");
+  chk(b, torch::kFloat, S, "b");
+  chk(ceP, torch::kFloat, S, "ceP");
+  chk(seP, torch::kFloat, S, "seP");
+  chk(ll, torch::kDouble, S, "ll");
+  chk(mm, torch::kDouble, S, "mm");
+  chk(nn1, torch::kDouble, S, "nn1");
+  TORCH_CHECK(rec.dim() == 2 && rec.size(0) == 2, "rec must be [2, max n0]");
+  chk(rec, torch::kFloat, rec.numel(), "rec");
+  ShapeletTab tab = {};
+  tab.src = ip(src); tab.cluster = ip(cluster); tab.n0 = ip(n0);
+  tab.beta = fp(beta); tab.off = ip(off); tab.coef = fp(coef);
+  tab.cxi = fp(cxi); tab.sxi = fp(sxi); tab.cphi = fp(cphi);
+  tab.sphi = fp(sphi); tab.psign = fp(psign); tab.a = fp(a); tab.b = fp(b);
+  tab.ceP = fp(ceP); tab.seP = fp(seP);
+  tab.ll = dp(ll); tab.mm = dp(mm); tab.nn1 = dp(nn1);
+  tab.rec = fp(rec); tab.S = (int)S; tab.nmax = (int)rec.size(1);
+  return tab;
+}
+
+// u, v, w: [R] float64 on one device, contiguous
+static void check_uvw(const torch::Tensor& u, const torch::Tensor& v,
+                      const torch::Tensor& w) {
+  TORCH_CHECK(u.is_cuda() && u.dim() == 1, "u must be a device tensor [R]");
+  for (const torch::Tensor* t : {&u, &v, &w})
+    TORCH_CHECK(t->device() == u.device() &&
+                t->scalar_type() == torch::kDouble && t->is_contiguous() &&
+                t->numel() == u.size(0),
+                "u, v, w must be contiguous [R] float64 on one device");
+}
+
 // Adds the shapelet sources of a ShapeletTable (hip_host.py) into `out`
 // [M, R, 4] complex64, in place, on the current stream.
 void shapelet_coh_add(
@@ -129,51 +193,21 @@ void shapelet_coh_add(
     int64_t Nbase, c10::optional<torch::Tensor> ejones, int64_t Nsta_ej) {
   const int64_t R = u.size(0);
   const int64_t S = src.size(0);
-  auto chk = [&](const torch::Tensor& t, torch::ScalarType ty, int64_t n,
-                 const char* name) {
-    TORCH_CHECK(t.device() == out.device(), name, " is on another device");
-    TORCH_CHECK(t.scalar_type() == ty, name, " has the wrong dtype");
-    TORCH_CHECK(t.is_contiguous() && t.numel() == n, name,
-                " must be contiguous with ", n, " elements");
-  };
-  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kComplexFloat &&
+  check_uvw(u, v, w);
+  TORCH_CHECK(out.device() == u.device() &&
+              out.scalar_type() == torch::kComplexFloat &&
               out.is_contiguous() && out.dim() == 3 && out.size(1) == R &&
               out.size(2) == 4, "out must be contiguous [M, R, 4] complex64");
-  chk(u, torch::kDouble, R, "u");
-  chk(v, torch::kDouble, R, "v");
-  chk(w, torch::kDouble, R, "w");
-  chk(src, torch::kInt, S, "src");
-  chk(cluster, torch::kInt, S, "cluster");
-  chk(n0, torch::kInt, S, "n0");
-  chk(beta, torch::kFloat, S, "beta");
-  chk(off, torch::kInt, S + 1, "off");
-  TORCH_CHECK(coef.scalar_type() == torch::kFloat && coef.is_contiguous() &&
-              coef.device() == out.device(), "coef must be contiguous float32");
-  chk(cxi, torch::kFloat, S, "cxi");
-  chk(sxi, torch::kFloat, S, "sxi");
-  chk(cphi, torch::kFloat, S, "cphi");
-  chk(sphi, torch::kFloat, S, "sphi");
-  chk(psign, torch::kFloat, S, "psign");
-  chk(a, torch::kFloat, S, "a");
-  chk(b, torch::kFloat, S, "b");
-  chk(ceP, torch::kFloat, S, "ceP");
-  chk(seP, torch::kFloat, S, "seP");
-  chk(ll, torch::kDouble, S, "ll");
-  chk(mm, torch::kDouble, S, "mm");
-  chk(nn1, torch::kDouble, S, "nn1");
-  TORCH_CHECK(rec.dim() == 2 && rec.size(0) == 2, "rec must be [2, max n0]");
-  chk(rec, torch::kFloat, rec.numel(), "rec");
-  chk(flux, torch::kFloat, 4 * S, "flux");
-  chk(r1, torch::kFloat, S, "r1");
+  ShapeletTab tab = shapelet_tab(u, src, cluster, n0, beta, off, coef, cxi,
+                                 sxi, cphi, sphi, psign, a, b, ceP, seP, ll,
+                                 mm, nn1, rec);
+  auto flt = [&](const torch::Tensor& t, int64_t n) {
+    return t.device() == u.device() && t.scalar_type() == torch::kFloat &&
+           t.is_contiguous() && t.numel() == n;
+  };
+  TORCH_CHECK(flt(flux, 4 * S), "flux must be contiguous [4, S] float32");
+  TORCH_CHECK(flt(r1, S), "r1 must be contiguous [S] float32");
   const BeamArgs bm = beam_args(beam, pairs, ejones, u, Nbase, Nsta_ej);
-  ShapeletTab tab = {};
-  tab.src = ip(src); tab.cluster = ip(cluster); tab.n0 = ip(n0);
-  tab.beta = fp(beta); tab.off = ip(off); tab.coef = fp(coef);
-  tab.cxi = fp(cxi); tab.sxi = fp(sxi); tab.cphi = fp(cphi);
-  tab.sphi = fp(sphi); tab.psign = fp(psign); tab.a = fp(a); tab.b = fp(b);
-  tab.ceP = fp(ceP); tab.seP = fp(seP);
-  tab.ll = dp(ll); tab.mm = dp(mm); tab.nn1 = dp(nn1);
-  tab.rec = fp(rec); tab.S = (int)S; tab.nmax = (int)rec.size(1);
   tab.flux = fp(flux); tab.r1 = fp(r1);
   CHECK_HIP(launch_shapelet_coh(rows_uvw(u, v, w), tab,
                                 {freq, fdelta2, tdelta}, bm, cptr(out),
@@ -404,6 +438,152 @@ torch::Tensor residuals_multifreq(
   CHECK_HIP(launch_residual_mf(a.rows, a.src, a.ch, bm, res, cptr(out),
                                cur_stream()));
   return out;
+}
+
+// What the two all-channels shapelet entry points share, checked: the rows,
+// the table with its [M + 1] entry prefix, the flux stack [F, 4, S] and r1
+// [S], and the channels. The caller guarantees that entry_off is
+// non-decreasing from 0 to S and that src holds source indices below K.
+struct ShapeletMfArgs {
+  MfArgs a;                 // rows and ch; src unused
+  ShapeletTabMF tab;
+};
+
+static ShapeletMfArgs shapelet_mf_args(
+    const torch::Tensor& u, const torch::Tensor& v, const torch::Tensor& w,
+    ShapeletTab t, const torch::Tensor& entry_off, const torch::Tensor& flux,
+    const torch::Tensor& r1, const torch::Tensor& freqs, double fdelta2,
+    double tdelta) {
+  check_uvw(u, v, w);
+  const int64_t R = u.size(0), S = t.S;
+  TORCH_CHECK(R >= 1 && R < (int64_t(1) << 31), "rows out of range");
+  TORCH_CHECK(S >= 1, "the shapelet table is empty");
+  auto on_dev = [&](const torch::Tensor& x, torch::ScalarType ty) {
+    return x.device() == u.device() && x.scalar_type() == ty &&
+           x.is_contiguous();
+  };
+  TORCH_CHECK(on_dev(freqs, torch::kDouble) && freqs.dim() == 1 &&
+              freqs.size(0) >= 1, "freqs must be contiguous [F] float64, "
+              "F >= 1");
+  const int64_t F = freqs.size(0);
+  TORCH_CHECK(on_dev(flux, torch::kFloat) && flux.dim() == 3 &&
+              flux.size(0) == F && flux.size(1) == 4 && flux.size(2) == S,
+              "flux must be contiguous [F, 4, S] float32");
+  TORCH_CHECK(on_dev(r1, torch::kFloat) && r1.numel() == S,
+              "r1 must be contiguous [S] float32");
+  TORCH_CHECK(on_dev(entry_off, torch::kInt) && entry_off.dim() == 1 &&
+              entry_off.size(0) >= 2,
+              "entry_off must be contiguous [M + 1] int32");
+  ShapeletMfArgs s = {};
+  s.a.rows = rows_uvw(u, v, w);
+  s.a.ch.freqs = dp(freqs);
+  s.a.ch.F = (int)F;
+  s.a.ch.fdelta2 = fdelta2;
+  s.a.ch.tdelta = tdelta;
+  s.a.ch.flux_stride = 4 * S;
+  s.tab.t = t;
+  s.tab.t.flux = fp(flux);
+  s.tab.t.r1 = fp(r1);
+  s.tab.entry_off = ip(entry_off);
+  s.tab.M = (int)entry_off.size(0) - 1;
+  return s;
+}
+
+// Adds the shapelet sources of all F channels into `out`, what
+// predict_coh_channels returned for the same rows, channels, mean and beam
+// (k_shapelet_coh_mf / _mean, with beam and/or ejones _bm / _ej): [F, M, R,
+// 4] complex64, or with mean [M, R, 4]. In place, on the current stream. K
+// is the source count of the pack, which beam and ejones must cover.
+void shapelet_coh_channels_add(
+    torch::Tensor out, torch::Tensor u, torch::Tensor v, torch::Tensor w,
+    torch::Tensor src, torch::Tensor cluster, torch::Tensor n0,
+    torch::Tensor beta, torch::Tensor off, torch::Tensor coef,
+    torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
+    torch::Tensor sphi, torch::Tensor psign, torch::Tensor a,
+    torch::Tensor b, torch::Tensor ceP, torch::Tensor seP,
+    torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
+    torch::Tensor rec, torch::Tensor entry_off, torch::Tensor flux,
+    torch::Tensor r1, torch::Tensor freqs, double fdelta2, double tdelta,
+    bool mean, int64_t K, c10::optional<torch::Tensor> beam,
+    c10::optional<torch::Tensor> ejones, c10::optional<torch::Tensor> pairs,
+    int64_t Nbase, int64_t Nsta_ej) {
+  const ShapeletMfArgs s = shapelet_mf_args(
+      u, v, w, shapelet_tab(u, src, cluster, n0, beta, off, coef, cxi, sxi,
+                            cphi, sphi, psign, a, b, ceP, seP, ll, mm, nn1,
+                            rec),
+      entry_off, flux, r1, freqs, fdelta2, tdelta);
+  const int64_t R = s.a.rows.R, F = s.a.ch.F, M = s.tab.M;
+  TORCH_CHECK(out.device() == u.device() &&
+              out.scalar_type() == torch::kComplexFloat &&
+              out.is_contiguous() && out.numel() == (mean ? 1 : F) * M * R * 4
+              && out.dim() == (mean ? 3 : 4) && out.size(-2) == R,
+              "out must be contiguous [F, M, R, 4] complex64, or [M, R, 4] "
+              "with mean");
+  const BeamChannels bm = beam_channels(beam, ejones, pairs, Nbase, Nsta_ej,
+                                        s.a, K, u);
+  CHECK_HIP(launch_shapelet_coh_mf(s.a.rows, s.tab, s.a.ch, bm, mean ? 1 : 0,
+                                   cptr(out), cur_stream()));
+}
+
+// Subtracts J_p C J_q^H of the shapelet sources of every cluster with
+// entries and skip == 0 from `out` [F, R, 4] complex64, what
+// residuals_multifreq returned for the same arguments
+// (k_shapelet_residual_mf, _bm, _ej). In place, on the current stream; J,
+// chunk_tab, pairs, skip and the caller's guarantees as there.
+void shapelet_residuals_add(
+    torch::Tensor out, torch::Tensor u, torch::Tensor v, torch::Tensor w,
+    torch::Tensor src, torch::Tensor cluster, torch::Tensor n0,
+    torch::Tensor beta, torch::Tensor off, torch::Tensor coef,
+    torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
+    torch::Tensor sphi, torch::Tensor psign, torch::Tensor a,
+    torch::Tensor b, torch::Tensor ceP, torch::Tensor seP,
+    torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
+    torch::Tensor rec, torch::Tensor entry_off, torch::Tensor flux,
+    torch::Tensor r1, torch::Tensor freqs, double fdelta2, double tdelta,
+    torch::Tensor J, torch::Tensor chunk_tab, torch::Tensor pairs,
+    c10::optional<torch::Tensor> skip, int64_t K,
+    c10::optional<torch::Tensor> beam, c10::optional<torch::Tensor> ejones,
+    int64_t Nsta_ej) {
+  const ShapeletMfArgs s = shapelet_mf_args(
+      u, v, w, shapelet_tab(u, src, cluster, n0, beta, off, coef, cxi, sxi,
+                            cphi, sphi, psign, a, b, ceP, seP, ll, mm, nn1,
+                            rec),
+      entry_off, flux, r1, freqs, fdelta2, tdelta);
+  const int64_t R = s.a.rows.R, F = s.a.ch.F, M = s.tab.M;
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType ty) {
+    return t.device() == u.device() && t.scalar_type() == ty &&
+           t.is_contiguous();
+  };
+  TORCH_CHECK(on_dev(out, torch::kComplexFloat) && out.dim() == 3 &&
+              out.size(0) == F && out.size(1) == R && out.size(2) == 4,
+              "out must be contiguous [F, R, 4] complex64");
+  TORCH_CHECK(on_dev(J, torch::kComplexFloat) && J.dim() == 3 &&
+              J.size(0) >= 1 && J.size(1) >= 1 && J.size(2) == 4,
+              "J must be contiguous [Mt, N, 4] complex64");
+  TORCH_CHECK(on_dev(chunk_tab, torch::kInt) && chunk_tab.dim() == 2 &&
+              chunk_tab.size(0) == M && chunk_tab.size(1) >= 1,
+              "chunk_tab must be contiguous [M, T] int32");
+  TORCH_CHECK(on_dev(pairs, torch::kInt) && pairs.dim() == 2 &&
+              pairs.size(0) >= 1 && pairs.size(1) == 2,
+              "pairs must be contiguous [Nbase, 2] int32");
+  TORCH_CHECK(chunk_tab.size(1) * pairs.size(0) == R,
+              "rows must be T * Nbase");
+  ResidualArgs res = {};
+  res.J = ccptr(J);
+  res.chunk_tab = ip(chunk_tab);
+  res.pairs = ip(pairs);
+  if (skip.has_value()) {
+    TORCH_CHECK(on_dev(*skip, torch::kInt) && skip->numel() == M,
+                "skip must be contiguous [M] int32");
+    res.skip = ip(*skip);
+  }
+  res.Nbase = (int)pairs.size(0);
+  res.T = (int)chunk_tab.size(1);
+  res.N = (int)J.size(1);
+  const BeamChannels bm = beam_channels(beam, ejones, pairs, pairs.size(0),
+                                        Nsta_ej, s.a, K, u);
+  CHECK_HIP(launch_shapelet_residual_mf(s.a.rows, s.tab, s.a.ch, bm, res,
+                                        cptr(out), cur_stream()));
 }
 
 // The four tensors both beam-gain entry points share: elem [N, Emax, 3]
@@ -718,6 +898,35 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("Nsta") = 0);
   m.attr("PREDICT_MF_NF") = PREDICT_MF_NF;
   m.attr("PREDICT_MF_NF_EJ") = PREDICT_MF_NF_EJ;
+  m.def("shapelet_coh_channels_add", &shapelet_coh_channels_add,
+        "add shapelet-source coherencies of all channels into out (gfx950)",
+        py::arg("out"), py::arg("u"), py::arg("v"), py::arg("w"),
+        py::arg("src"), py::arg("cluster"), py::arg("n0"), py::arg("beta"),
+        py::arg("off"), py::arg("coef"), py::arg("cxi"), py::arg("sxi"),
+        py::arg("cphi"), py::arg("sphi"), py::arg("psign"), py::arg("a"),
+        py::arg("b"), py::arg("ceP"), py::arg("seP"), py::arg("ll"),
+        py::arg("mm"), py::arg("nn1"), py::arg("rec"), py::arg("entry_off"),
+        py::arg("flux"), py::arg("r1"), py::arg("freqs"), py::arg("fdelta2"),
+        py::arg("tdelta"), py::arg("mean"), py::arg("K"),
+        py::arg("beam") = py::none(), py::arg("ejones") = py::none(),
+        py::arg("pairs") = py::none(), py::arg("Nbase") = 0,
+        py::arg("Nsta") = 0);
+  m.def("shapelet_residuals_add", &shapelet_residuals_add,
+        "subtract the shapelet-source model of all channels from out "
+        "(gfx950)",
+        py::arg("out"), py::arg("u"), py::arg("v"), py::arg("w"),
+        py::arg("src"), py::arg("cluster"), py::arg("n0"), py::arg("beta"),
+        py::arg("off"), py::arg("coef"), py::arg("cxi"), py::arg("sxi"),
+        py::arg("cphi"), py::arg("sphi"), py::arg("psign"), py::arg("a"),
+        py::arg("b"), py::arg("ceP"), py::arg("seP"), py::arg("ll"),
+        py::arg("mm"), py::arg("nn1"), py::arg("rec"), py::arg("entry_off"),
+        py::arg("flux"), py::arg("r1"), py::arg("freqs"), py::arg("fdelta2"),
+        py::arg("tdelta"), py::arg("J"), py::arg("chunk_tab"),
+        py::arg("pairs"), py::arg("skip"), py::arg("K"),
+        py::arg("beam") = py::none(), py::arg("ejones") = py::none(),
+        py::arg("Nsta") = 0);
+  m.attr("SHAPELET_MF_NF") = SHAPELET_MF_NF;
+  m.attr("SHAPELET_MF_NF_EJ") = SHAPELET_MF_NF_EJ;
   m.def("array_beam_gains", &array_beam_gains,
         "station array-factor gains [T, K, N] (gfx950)", py::arg("elem"),
         py::arg("nelem"), py::arg("du"), py::arg("below"), py::arg("kf"));

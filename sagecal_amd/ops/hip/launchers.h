@@ -44,6 +44,16 @@ struct ShapeletTab {
   const float* r1;          // [S]
 };
 
+// Shapelet mode table of the all-channels kernels (shapelet_mf.hip): the
+// table above, its `cluster` unread, with t.flux the [F, 4, S] stack of the
+// channels' fluxes (rows Channels.flux_stride floats apart) and t.r1 [S],
+// and the entries of cluster ci at entry_off[ci] <= s < entry_off[ci + 1].
+struct ShapeletTabMF {
+  ShapeletTab t;
+  const int* entry_off;     // [M + 1]
+  int M;
+};
+
 struct Channel {
   double freq;
   double fdelta2;           // channel halfwidth [Hz]
@@ -128,6 +138,27 @@ hipError_t launch_predict_coh_mf(RowsUVW rows, SourceArrays src, Channels ch,
 hipError_t launch_residual_mf(RowsUVW rows, SourceArrays src, Channels ch,
                               BeamChannels bm, ResidualArgs res, float2* out,
                               hipStream_t stream);
+
+// The shapelet sources of all channels in one launch, ADDED into the `out`
+// of the launcher above of the same shape (launch_predict_coh_mf with the
+// same mean, launch_residual_mf), after it on the same stream and with the
+// same ch, bm and res. Channels a thread carries per pass, without E-Jones
+// and with:
+#ifndef SHAPELET_MF_NF
+#define SHAPELET_MF_NF 2
+#endif
+#ifndef SHAPELET_MF_NF_EJ
+#define SHAPELET_MF_NF_EJ 2
+#endif
+// hipErrorInvalidValue: what those two launchers refuse (res.x is not
+// read: out holds x minus the model so far), S < 1, M < 1 or no entry_off.
+hipError_t launch_shapelet_coh_mf(RowsUVW rows, ShapeletTabMF tab,
+                                  Channels ch, BeamChannels bm, int mean,
+                                  float2* out, hipStream_t stream);
+hipError_t launch_shapelet_residual_mf(RowsUVW rows, ShapeletTabMF tab,
+                                       Channels ch, BeamChannels bm,
+                                       ResidualArgs res, float2* out,
+                                       hipStream_t stream);
 
 hipError_t launch_array_beam(
     const double* elem, const int* nelem, const double* du,

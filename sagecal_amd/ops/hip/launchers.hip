@@ -4,6 +4,7 @@
 #include "launchers.h"
 #include "predict.hip"
 #include "predict_mf.hip"
+#include "shapelet_mf.hip"
 #include "jtj.hip"
 #include "cholesky.hip"
 #include "element_beam.hip"
@@ -105,6 +106,58 @@ hipError_t launch_residual_mf(RowsUVW rows, SourceArrays src, Channels ch,
   else
     hipLaunchKernelGGL(k_residual_mf_ej, grid, dim3(128), 0, stream, rows,
                        src, ch, bm, res, out);
+  return hipGetLastError();
+}
+
+static bool shapelet_tab_ok(const ShapeletTabMF& tab) {
+  return tab.t.S >= 1 && tab.M >= 1 && tab.entry_off != nullptr &&
+         tab.t.flux != nullptr && tab.t.r1 != nullptr;
+}
+
+hipError_t launch_shapelet_coh_mf(RowsUVW rows, ShapeletTabMF tab,
+                                  Channels ch, BeamChannels bm, int mean,
+                                  float2* out, hipStream_t stream) {
+  dim3 grid;
+  const int mode = mf_beam_mode(bm, rows.R);
+  if (mode < 0 || ch.freqs == nullptr || !shapelet_tab_ok(tab) ||
+      !mf_grid(rows.R, ch.F, mode == MF_EJ ? SH_NF_EJ : SH_NF, !mean, &grid))
+    return hipErrorInvalidValue;
+  if (mode == MF_PLAIN)
+    hipLaunchKernelGGL(mean ? k_shapelet_coh_mean : k_shapelet_coh_mf, grid,
+                       dim3(128), 0, stream, rows, tab, ch, out);
+  else if (mode == MF_GAIN)
+    hipLaunchKernelGGL(mean ? k_shapelet_coh_mean_bm : k_shapelet_coh_mf_bm,
+                       grid, dim3(128), 0, stream, rows, tab, ch, bm, out);
+  else
+    hipLaunchKernelGGL(mean ? k_shapelet_coh_mean_ej : k_shapelet_coh_mf_ej,
+                       grid, dim3(128), 0, stream, rows, tab, ch, bm, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_shapelet_residual_mf(RowsUVW rows, ShapeletTabMF tab,
+                                       Channels ch, BeamChannels bm,
+                                       ResidualArgs res, float2* out,
+                                       hipStream_t stream) {
+  dim3 grid;
+  const int mode = mf_beam_mode(bm, rows.R);
+  if (mode < 0 || ch.freqs == nullptr || !shapelet_tab_ok(tab) ||
+      !mf_grid(rows.R, ch.F, mode == MF_EJ ? SH_NF_EJ : SH_NF, true, &grid) ||
+      res.J == nullptr || res.chunk_tab == nullptr || res.pairs == nullptr ||
+      res.Nbase < 1 || res.T < 1 || res.N < 1 ||
+      (long long)res.T * res.Nbase != rows.R)
+    return hipErrorInvalidValue;
+  if (mode != MF_PLAIN && (bm.pairs != res.pairs || bm.Nbase != res.Nbase ||
+                           bm.T != res.T))
+    return hipErrorInvalidValue;
+  if (mode == MF_PLAIN)
+    hipLaunchKernelGGL(k_shapelet_residual_mf, grid, dim3(128), 0, stream,
+                       rows, tab, ch, res, out);
+  else if (mode == MF_GAIN)
+    hipLaunchKernelGGL(k_shapelet_residual_mf_bm, grid, dim3(128), 0, stream,
+                       rows, tab, ch, bm, res, out);
+  else
+    hipLaunchKernelGGL(k_shapelet_residual_mf_ej, grid, dim3(128), 0, stream,
+                       rows, tab, ch, bm, res, out);
   return hipGetLastError();
 }
 

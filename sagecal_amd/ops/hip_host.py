@@ -50,6 +50,10 @@ class ShapeletTable:
       ll, mm, nn1        float64 [S]  direction cosines
       rec                float [2, max n0]  recurrence constants
                          sqrt(2/n), sqrt((n-1)/n); rec[:,0] unused
+      entry_off          int32 [M+1]  entries of cluster ci at
+                         entry_off[ci] <= s < entry_off[ci+1]; read by the
+                         all-channels kernels only and not in FIELDS, the
+                         positional arguments of shapelet_coh_add
 
     `float` is float32, the kernel's layout; dtype=torch.float64 keeps the
     host-computed values unrounded for fp64 checks of the mirror. The
@@ -100,7 +104,9 @@ class ShapeletTable:
             np.ascontiguousarray(x), dtype=torch.float64).to(
                 device=device, dtype=dt).contiguous()
         self.src = i32(src)
-        self.cluster = i32(np.searchsorted(co, src, side='right') - 1)
+        cluster = np.searchsorted(co, src, side='right') - 1
+        self.cluster = i32(cluster)
+        self.entry_off = i32(np.searchsorted(cluster, np.arange(self.M + 1)))
         self.n0 = i32(n0)
         self.off = i32(off)
         self.beta = flt([sh[1] for _, sh in items])
@@ -240,6 +246,7 @@ class GPUPack:
         self._flux_cache = {}
         self._sh_flux_cache = {}
         self._stack_cache = {}
+        self._sh_stack_cache = {}
 
     def _flog(self, freq):
         """Log-polynomial spectral exponent per source at `freq`."""
@@ -302,6 +309,21 @@ class GPUPack:
         [4, S] float32 in table order."""
         self.fluxes_at(freq, freq0)
         return self._sh_flux_cache[round(float(freq), 3)]
+
+    def shapelet_flux_stack(self, freqs, freq0):
+        """Fluxes [F, 4, S] float32 of the shapelet sources for the
+        all-channels kernels: row f is shapelet_fluxes_at(freqs[f], freq0).
+        Remembered per frequency tuple, like flux_stack."""
+        key = (tuple(round(float(f), 3) for f in freqs),
+               round(float(freq0), 3))
+        hit = self._sh_stack_cache.get(key)
+        if hit is None:
+            if len(self._sh_stack_cache) > 16:   # bound long multi-MS runs
+                self._sh_stack_cache.pop(next(iter(self._sh_stack_cache)))
+            hit = self._sh_stack_cache[key] = torch.stack(
+                [self.shapelet_fluxes_at(float(f), freq0)
+                 for f in freqs]).contiguous()
+        return hit
 
     def r1_for(self, dec0):
         """Time-smear source-distance term sqrt(ll^2+(sin(dec0) mm)^2)
@@ -455,12 +477,26 @@ def _mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0):
             gp.stype, gp.cluster_off, fq, float(fdelta) * 0.5, float(tdelta))
 
 
-def _mf_pack(pack, device, what):
+def _mf_pack(pack, device, what, shapelets=False):
     gp = pack if isinstance(pack, GPUPack) else gpu_pack(pack, device)
-    if gp.sh is not None:
-        raise ValueError(f"{what} has no shapelet sources; predict this "
+    if gp.sh is not None and not shapelets:
+        raise ValueError(f"{what} takes shapelet sources with "
+                         "shapelets=True only; without it predict this "
                          "pack channel by channel with predict_coh")
     return gp
+
+
+def _shapelet_mf_args(gp, src_args, freqs, freq0):
+    """Positional arguments u .. tdelta of the extension's all-channels
+    shapelet entry points, from those of the main call (_mf_source_args):
+    the same rows, r1, frequencies and widths, the pack's mode table and
+    the shapelet flux stack. Device work only, no synchronisation."""
+    tab = gp.sh
+    u, v, w = src_args[:3]
+    r1, fq, fdelta2, tdelta = src_args[14], *src_args[17:]
+    return (u, v, w, *(getattr(tab, k) for k in tab.FIELDS), tab.entry_off,
+            gp.shapelet_flux_stack(freqs, freq0),
+            r1.index_select(0, tab.src), fq, fdelta2, tdelta)
 
 
 def _check_beam_channels(beam, ejones, pairs, Nbase, F, R, K, dev,
@@ -537,7 +573,7 @@ def _check_beam_channels(beam, ejones, pairs, Nbase, F, R, K, dev,
 
 def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
                          reduce=None, beam=None, ejones=None, pairs=None,
-                         Nbase=0):
+                         Nbase=0, shapelets=False):
     """Coherencies of every channel of `freqs` in one launch
     (k_predict_coh_mf): [F, M, R, 2, 2] complex64, channel f equal to
     predict_coh at freqs[f] (bit for bit on point sources; an extended
@@ -555,14 +591,23 @@ def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
     the _ej kernels with patterns. With neither the call is what it was
     without these arguments.
 
-    A pack with shapelet sources raises ValueError. Empty freqs or no rows
-    return an empty tensor without a launch. Once the pack and the flux
-    stack of this frequency tuple are on the device, and after the first
-    call with a new pair table (whose index range is read back), the path
-    has no host synchronisation."""
+    A pack with shapelet sources raises ValueError, unless shapelets=True:
+    then a second launch on the same stream (k_shapelet_coh_mf /
+    k_shapelet_coh_mean, with a beam their _bm / _ej variants) adds the
+    shapelet sources of every channel into the result, channel f equal to
+    predict_coh at freqs[f] up to rounding, with the same beam, ejones and
+    pairs and under the checks already made. SAGECAL_SHAPELET_HOST is not
+    consulted on this path: there is no torch mirror of these kernels. On a
+    pack without shapelet sources shapelets=True changes nothing.
+
+    Empty freqs or no rows return an empty tensor without a launch. Once
+    the pack, its mode table and the flux stacks of this frequency tuple
+    are on the device, and after the first call with a new pair table
+    (whose index range is read back), the path has no host
+    synchronisation."""
     if reduce not in (None, 'mean'):
         raise ValueError(f"reduce must be None or 'mean', got {reduce!r}")
-    gp = _mf_pack(pack, u.device, 'predict_coh_channels')
+    gp = _mf_pack(pack, u.device, 'predict_coh_channels', shapelets)
     freqs = [float(f) for f in freqs]
     F, R = len(freqs), int(u.shape[0])
     if reduce == 'mean' and F == 0:
@@ -574,15 +619,18 @@ def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
     if beam is not None or ejones is not None:
         bm = _check_beam_channels(beam, ejones, pairs, Nbase, F, R, gp.K,
                                   u.device)
-    out = _ext().predict_coh_channels(
-        *_mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0),
-        mean=reduce == 'mean', **bm)
+    args = _mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0)
+    out = _ext().predict_coh_channels(*args, mean=reduce == 'mean', **bm)
+    if gp.sh is not None:
+        _ext().shapelet_coh_channels_add(
+            out, *_shapelet_mf_args(gp, args, freqs, freq0),
+            mean=reduce == 'mean', K=gp.K, **bm)
     return out.view(*out.shape[:-1], 2, 2)
 
 
 def residuals_multifreq(pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
                         J, chunk_tab, pairs, subtract=None, beam=None,
-                        ejones=None):
+                        ejones=None, shapelets=False):
     """x[f] - sum over subtracted clusters of J_p C_f J_q^H for every
     channel in one launch (k_residual_mf); the coherencies C_f are those of
     predict_coh_channels, with the station beam of `beam` [F, T, K, N]
@@ -596,9 +644,17 @@ def residuals_multifreq(pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
     keeps x and looks up no beam. Returns [F, R, 2, 2] complex64. The first call with a new pair
     or chunk table reads its index range back for the bounds check; after
     that, and once pack and flux stack are on the device, the path has no
-    host synchronisation."""
+    host synchronisation.
+
+    A pack with shapelet sources raises ValueError, unless shapelets=True:
+    then k_shapelet_residual_mf (or its _bm / _ej variant), launched after
+    the main kernel on the same stream, subtracts J_p C_f J_q^H of the
+    shapelet sources of every subtracted cluster from the result, with the
+    same tables and beam. SAGECAL_SHAPELET_HOST is not consulted on this
+    path; on a pack without shapelet sources shapelets=True changes
+    nothing."""
     dev = u.device
-    gp = _mf_pack(pack, dev, 'residuals_multifreq')
+    gp = _mf_pack(pack, dev, 'residuals_multifreq', shapelets)
     freqs = [float(f) for f in freqs]
     F, R = len(freqs), int(u.shape[0])
     if x.dim() != 4 or tuple(x.shape) != (F, R, 2, 2):
@@ -632,11 +688,15 @@ def residuals_multifreq(pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
         bm = _check_beam_channels(beam, ejones, pairs, 0, F, R, gp.K, dev,
                                   negative_ok=True, Nsta=N)
         bm = {k: bm[k] for k in ('beam', 'ejones', 'Nsta') if k in bm}
+    args = _mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0)
+    J4 = J.to(torch.complex64).reshape(Mt, N, 4).contiguous()
     out = _ext().residuals_multifreq(
-        x.to(torch.complex64).reshape(F, R, 4).contiguous(),
-        *_mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0),
-        J.to(torch.complex64).reshape(Mt, N, 4).contiguous(), chunk_tab,
-        pairs, skip, **bm)
+        x.to(torch.complex64).reshape(F, R, 4).contiguous(), *args, J4,
+        chunk_tab, pairs, skip, **bm)
+    if gp.sh is not None:
+        _ext().shapelet_residuals_add(
+            out, *_shapelet_mf_args(gp, args, freqs, freq0), J4, chunk_tab,
+            pairs, skip, K=gp.K, **bm)
     return out.view(F, R, 2, 2)
 
 

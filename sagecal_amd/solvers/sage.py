@@ -125,7 +125,7 @@ def precalc_coherencies(pack, tile, device=None, discrete=True):
         # one launch: the channels are summed in the kernel, none stored
         return ops.predict_coh_channels(pack, u, v, w, freqs, tile.freq0,
                                         fdelta_ch, tile.tdelta, tile.dec0,
-                                        reduce='mean')
+                                        reduce='mean', shapelets=True)
     acc = None
     for f in freqs:
         c = ops.predict_coh(pack, u, v, w, float(f), tile.freq0,
@@ -136,11 +136,15 @@ def precalc_coherencies(pack, tile, device=None, discrete=True):
 
 def _all_channels_ok(pack, t):
     """Whether the all-channels kernels (ops.predict_coh_channels,
-    ops.residuals_multifreq) take this predict: device tensors, no shapelet
-    sources. SAGECAL_RESIDUAL_LOOP=1 forces the per-channel loop, for A/B
-    runs; SAGECAL_FORCE_REFERENCE=1 implies it."""
+    ops.residuals_multifreq) take this predict: device tensors, and no
+    shapelet sources unless SAGECAL_SHAPELET_CHANNELS=1 opts into the
+    all-channels shapelet kernels (callers pass shapelets=True).
+    SAGECAL_RESIDUAL_LOOP=1 forces the per-channel loop, for A/B runs;
+    SAGECAL_FORCE_REFERENCE=1 implies it."""
     import os
-    return (t.is_cuda and not getattr(pack, 'shapelets', None)
+    return (t.is_cuda
+            and (not getattr(pack, 'shapelets', None)
+                 or os.environ.get('SAGECAL_SHAPELET_CHANNELS') == '1')
             and os.environ.get('SAGECAL_RESIDUAL_LOOP') != '1'
             and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
 
@@ -530,7 +534,7 @@ def calculate_residuals_multifreq(state, pack, tile, bb, ccid=None, rho=0.0,
             fdelta_ch, tile.tdelta, tile.dec0, state.J,
             _chunk_table(state, T, Nbase, dev), lay.pairs,
             _subtract_mask(state, skip, dev) if skip else None,
-            **(beam or {})).to(tile.xo.dtype)
+            shapelets=True, **(beam or {})).to(tile.xo.dtype)
     else:
         out = torch.empty_like(tile.xo)
         for fi, f in enumerate(tile.freqs):

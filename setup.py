@@ -16,6 +16,10 @@ from torch.utils.cpp_extension import BuildExtension, CUDAExtension
 ROOT = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(ROOT, 'sagecal_amd', 'ops', 'hip')
 
+# SAGECAL_HIP_DEFINES="-DSHAPELET_MF_NF=4 ..." overrides the #ifndef-guarded
+# constants of launchers.h, for the channels-per-pass sweeps
+DEFINES = os.environ.get('SAGECAL_HIP_DEFINES', '').split()
+
 ext = CUDAExtension(
     name='sagecal_amd.ops.hip.dirac_hip',
     sources=[
@@ -23,8 +27,8 @@ ext = CUDAExtension(
         os.path.join(SRC, 'launchers.hip'),
     ],
     extra_compile_args={
-        'cxx': ['-O3', '-std=c++17'],
-        'nvcc': ['-O3', '-std=c++17', '--offload-arch=gfx950'],
+        'cxx': ['-O3', '-std=c++17'] + DEFINES,
+        'nvcc': ['-O3', '-std=c++17', '--offload-arch=gfx950'] + DEFINES,
     },
 )
 

@@ -25,6 +25,14 @@ mean of the beamed predicts: one predict_coh_channels(reduce='mean') call
 against the loop over predict_coh. The loop is what runs without the
 all-channels kernels, selected by the same switch.
 
+--shapelets COUNT,N0 turns COUNT sources of the sky into shapelets of order
+N0 (source j is source j // 10 of cluster j % 10; coefficients as in
+tools/bench_shapelet_predict.py, whose "few" and "many" skies are 2,3 and
+32,8) and times the all-channels shapelet kernels, which the fused path then
+takes through SAGECAL_SHAPELET_CHANNELS=1, against the per-channel loop, the
+only path such a pack had before them. The data stay those of the sky
+without shapelets: the timings do not read them. Combines with --beam.
+
 Kernel durations come from a second run under the profiler, which slows
 the host and so gets no timings of its own:
 
@@ -53,6 +61,33 @@ SHAPE = dict(stations=64, dirs=10, srcs=5, tilesz=60, intervals=16, chan=8,
              freq0=150e6, bandwidth=180e3, shapelet_dirs=0)
 WARMUP, PROFILE_CALLS = 2, 2
 SWITCH = 'SAGECAL_RESIDUAL_LOOP'
+SHAPELET_SWITCH = 'SAGECAL_SHAPELET_CHANNELS'
+
+
+def shapelet_pack(count, n0):
+    """The sky of bench.build_problem at SHAPE (same seed, clusters and
+    chunk counts) with `count` of its sources turned into shapelets."""
+    from sagecal_amd import sky
+    from sagecal_amd.ops.reference import SourcePack
+    srcs, clist = sky.make_synthetic_sky(
+        M=SHAPE['dirs'], nsrc_per_cluster=SHAPE['srcs'], seed=17)
+    clist = [(cid, SHAPE['intervals'] * nchunk, names)
+             for cid, nchunk, names in clist]
+    if not 0 < count <= SHAPE['dirs'] * SHAPE['srcs']:
+        sys.exit(f'--shapelets: COUNT must be 1..'
+                 f"{SHAPE['dirs'] * SHAPE['srcs']}")
+    rng = np.random.default_rng(23)
+    k = np.arange(n0)
+    decay = 1.0 / (1.0 + k[None, :] + k[:, None])
+    for j in range(count):
+        s = srcs[clist[j % SHAPE['dirs']][2][j // SHAPE['dirs']]]
+        s.stype = 4
+        s.eX = s.eY = 1.0
+        s.sh_n0 = n0
+        s.sh_beta = 1e-3
+        s.sh_coeff = (rng.standard_normal((n0, n0)) * decay).reshape(-1)
+    return SourcePack(sky.build_clusters(srcs, clist, 0.0, np.pi / 4,
+                                         SHAPE['freq0']))
 
 
 def merge_kernels(out, stats_csv):
@@ -108,7 +143,7 @@ def beamed_functions(mode, sage, state, pack, tile, bb):
             return ops.predict_coh_channels(
                 pack, tile.u, tile.v, tile.w, freqs, tile.freq0, fdch,
                 tile.tdelta, tile.dec0, reduce='mean', pairs=pairs,
-                Nbase=Nbase, **bm)
+                Nbase=Nbase, shapelets=True, **bm)
         acc = None
         for f in freqs:
             c = coh_fn(f)
@@ -126,6 +161,7 @@ def main():
     ap.add_argument('--out', help='result JSON path')
     ap.add_argument('--runs', type=int, default=10)
     ap.add_argument('--beam', type=int, choices=(1, 2, 3), metavar='MODE')
+    ap.add_argument('--shapelets', metavar='COUNT,N0')
     ap.add_argument('--profile-run', action='store_true')
     ap.add_argument('--merge-kernels', metavar='CSV')
     args = ap.parse_args()
@@ -139,10 +175,13 @@ def main():
     if not torch.cuda.is_available():
         sys.exit('bench_residual_predict: no GPU, nothing to measure')
     import bench
+    from sagecal_amd.ops import hip_host
     from sagecal_amd.solvers import sage
     dev = 'cuda:0'
     pack, ms, tile, bb = bench.build_problem(SimpleNamespace(**SHAPE), dev,
                                              torch.float32)
+    if args.shapelets:
+        pack = shapelet_pack(*(int(x) for x in args.shapelets.split(',')))
     state = sage.CalState(pack, SHAPE['stations'], device=dev,
                           dtype=torch.complex64)
     g = torch.Generator().manual_seed(7)
@@ -152,10 +191,13 @@ def main():
     def call(fn, loop):
         if loop:
             os.environ[SWITCH] = '1'
+        elif args.shapelets:
+            os.environ[SHAPELET_SWITCH] = '1'
         try:
             return fn()
         finally:
             os.environ.pop(SWITCH, None)
+            os.environ.pop(SHAPELET_SWITCH, None)
 
     fns = {'calculate_residuals_multifreq':
            lambda: sage.calculate_residuals_multifreq(state, pack, tile, bb),
@@ -177,7 +219,9 @@ def main():
            'rows': int(tile.u.shape[0]), 'channels': len(tile.freqs),
            'clusters': pack.M, 'sources': int(pack.cluster_off[-1]),
            'chunks': state.Mt, 'warmup': WARMUP, 'runs': args.runs,
-           'beam_mode': args.beam,
+           'beam_mode': args.beam, 'shapelets': args.shapelets,
+           'shapelet_nf': [int(hip_host._ext().SHAPELET_MF_NF),
+                           int(hip_host._ext().SHAPELET_MF_NF_EJ)],
            'order': 'fused, loop, fused, loop, ...', 'functions': {}}
     for name, fn in fns.items():
         rec = {p: {'ms_per_call': []} for p, _ in paths}
