@@ -231,8 +231,104 @@ def update_nu_aecm(w, nu_old, **kw):
     return R.update_nu_aecm(w, nu_old, **kw)
 
 
+def lbfgs_channels_on():
+    """SAGECAL_LBFGS_CHANNELS=1 opts into the fused multi-channel LBFGS
+    kernels (lbfgs_cost_grad_channels) wherever a device cost/gradient is
+    evaluated; off by default, and SAGECAL_FORCE_REFERENCE=1 overrides
+    it."""
+    return (os.environ.get('SAGECAL_LBFGS_CHANNELS') == '1'
+            and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
+
+
+_lbfgs_tab_memo = {}   # chunk tables and pair tables of lbfgs_cost_grad
+
+
+def _memo(key, build):
+    hit = _lbfgs_tab_memo.get(key)
+    if hit is None:
+        if len(_lbfgs_tab_memo) > 64:    # bound long multi-MS runs
+            _lbfgs_tab_memo.pop(next(iter(_lbfgs_tab_memo)))
+        hit = _lbfgs_tab_memo[key] = build()
+    return hit
+
+
+def lbfgs_chunk_table(chunk_off, nchunks, T, device):
+    """[M, T] int32 on `device`: chunk_off[ci] + R.chunk_rows_for per
+    timeslot, the table lbfgs_cost_grad_channels takes; one tensor per
+    (nchunks, chunk_off, T, device)."""
+    nchunks = [int(n) for n in nchunks]
+    chunk_off = [int(o) for o in chunk_off]
+
+    def build():
+        rows = []
+        for ci, off in enumerate(chunk_off):
+            r = R.chunk_rows_for(ci, nchunks, T, 1, T, 'cpu')
+            if r is None:
+                r = torch.zeros(T, dtype=torch.long)
+            rows.append(r + off)
+        return torch.stack(rows).to(device=device, dtype=torch.int32)
+    return _memo((tuple(nchunks), tuple(chunk_off), T, str(device)), build)
+
+
+def lbfgs_pair_table(bb, Nbase, device):
+    """bb[:Nbase] as the int32 pair table on `device`, one tensor per bb
+    tensor: the kernels' index tables are remembered per pair table."""
+    build = lambda: bb[:Nbase].to(device=device,
+                                  dtype=torch.int32).contiguous()
+    try:
+        return _memo((obj_token(bb), bb._version, Nbase, str(device)), build)
+    except RuntimeError:                 # inference tensor: no version
+        return build()
+
+
+def lbfgs_cost_grad_channels(xs, cohs, J, chunk_tab, pairs, robust_nu=None):
+    """(cost, grad [Mt*N*8]) of the LBFGS objective over all channels: the
+    sum over f of lbfgs_cost_grad(xs[f], cohs[f], ...) with xs [F, R, 2, 2],
+    cohs [F, M, R, 2, 2], J [Mt, N, 2, 2], chunk_tab [M, T] global chunk id
+    per (cluster, timeslot), pairs [Nbase, 2], rows r = t*Nbase + b; a row
+    whose pair has a negative entry adds nothing. On the GPU three launches
+    of the kernels of lbfgs_mf.hip; elsewhere that sum over
+    R.lbfgs_cost_grad, in the input precision."""
+    if _use_hip(xs):
+        from . import hip_host
+        return hip_host.lbfgs_cost_grad_channels(xs, cohs, J, chunk_tab,
+                                                 pairs, robust_nu)
+    F, Rn = int(xs.shape[0]), int(xs.shape[1])
+    M, T, Nbase = int(cohs.shape[1]), int(chunk_tab.shape[1]), \
+        int(pairs.shape[0])
+    if tuple(cohs.shape) != (F, M, Rn, 2, 2) or chunk_tab.shape[0] != M \
+            or T * Nbase != Rn:
+        raise ValueError("xs [F, R, 2, 2], cohs [F, M, R, 2, 2], chunk_tab "
+                         "[M, T] and pairs [Nbase, 2] with T * Nbase rows")
+    Mt, N = int(J.shape[0]), int(J.shape[1])
+    bb = pairs.to(device=xs.device, dtype=torch.long).repeat(T, 1)
+    live = (bb >= 0).all(dim=1)[:, None, None]
+    bb = bb.clamp_min(0)        # flagged rows get x = coh = 0: res = 0
+    # R.lbfgs_cost_grad with one chunk per (cluster, timeslot): chunk
+    # ci*T + t holds J[chunk_tab[ci, t]], whatever the table looks like
+    tab = chunk_tab.to(device=xs.device, dtype=torch.long).reshape(-1)
+    Jt = J[tab]
+    chunk_off, nchunks = [ci * T for ci in range(M)], [T] * M
+    cost = xs.real.new_zeros(())
+    grad = xs.real.new_zeros(Mt, N * 8)
+    zero = xs.new_zeros(())
+    for f in range(F):
+        c, g = R.lbfgs_cost_grad(
+            torch.where(live, xs[f], zero), torch.where(live, cohs[f], zero),
+            Jt, chunk_off, nchunks, bb, T, Nbase, robust_nu)
+        cost = cost + c
+        grad.index_add_(0, tab, g.reshape(M * T, N * 8))
+    return cost, grad.reshape(-1)
+
+
 def lbfgs_cost_grad(x, cohs, J_packed, chunk_off, nchunks, bb, T, Nbase,
                     robust_nu=None, weights=None):
+    if _use_hip(x) and lbfgs_channels_on() and weights is None \
+            and x.shape[0] == T * Nbase:
+        return lbfgs_cost_grad_channels(
+            x[None], cohs[None], J_packed,
+            lbfgs_chunk_table(chunk_off, nchunks, T, x.device),
+            lbfgs_pair_table(bb, Nbase, x.device), robust_nu)
     if _use_hip(x):
         from . import hip_host
         return hip_host.lbfgs_cost_grad(x, cohs, J_packed, chunk_off,

@@ -847,8 +847,89 @@ std::vector<torch::Tensor> jtr_grad(
   return {g, cost};
 }
 
+// Cost and gradient of the multi-channel LBFGS objective (lbfgs_mf.hip): xs
+// [F, R, 4], cohs [F, M, R, 4] and J [Mt, N, 4] complex64, chunk_tab [M, T]
+// and pairs [Nbase, 2] int32 with R == T * Nbase, and the index tables of
+// hip_host._lbfgs_tables: ext [E, 4], ext_off [Mt + 1], sta_off [N + 1],
+// sta_ent. robust_nu <= 0: Gaussian cost. Returns (cost [] float32, grad
+// [Mt*N*8] float32). The caller guarantees chunk ids below Mt, pair entries
+// below N and tables that match chunk_tab and pairs.
+std::vector<torch::Tensor> lbfgs_cost_grad_channels(
+    torch::Tensor xs, torch::Tensor cohs, torch::Tensor J,
+    torch::Tensor chunk_tab, torch::Tensor pairs, torch::Tensor ext,
+    torch::Tensor ext_off, torch::Tensor sta_off, torch::Tensor sta_ent,
+    double robust_nu) {
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType ty) {
+    return t.is_cuda() && t.device() == xs.device() &&
+           t.scalar_type() == ty && t.is_contiguous();
+  };
+  TORCH_CHECK(on_dev(xs, torch::kComplexFloat) && xs.dim() == 3 &&
+              xs.size(0) >= 1 && xs.size(1) >= 1 && xs.size(2) == 4,
+              "xs must be contiguous [F, R, 4] complex64 on the device");
+  const int64_t F = xs.size(0), R = xs.size(1);
+  TORCH_CHECK(on_dev(cohs, torch::kComplexFloat) && cohs.dim() == 4 &&
+              cohs.size(0) == F && cohs.size(1) >= 1 && cohs.size(2) == R &&
+              cohs.size(3) == 4,
+              "cohs must be contiguous [F, M, R, 4] complex64");
+  const int64_t M = cohs.size(1);
+  TORCH_CHECK(on_dev(J, torch::kComplexFloat) && J.dim() == 3 &&
+              J.size(0) >= 1 && J.size(1) >= 1 && J.size(2) == 4,
+              "J must be contiguous [Mt, N, 4] complex64");
+  const int64_t Mt = J.size(0), N = J.size(1);
+  TORCH_CHECK(on_dev(chunk_tab, torch::kInt) && chunk_tab.dim() == 2 &&
+              chunk_tab.size(0) == M && chunk_tab.size(1) >= 1,
+              "chunk_tab must be contiguous [M, T] int32");
+  TORCH_CHECK(on_dev(pairs, torch::kInt) && pairs.dim() == 2 &&
+              pairs.size(0) >= 1 && pairs.size(1) == 2,
+              "pairs must be contiguous [Nbase, 2] int32");
+  const int64_t T = chunk_tab.size(1), Nbase = pairs.size(0);
+  TORCH_CHECK(T * Nbase == R && R < (int64_t(1) << 31),
+              "rows must be T * Nbase, below 2^31");
+  TORCH_CHECK(on_dev(ext, torch::kInt) && ext.dim() == 2 &&
+              ext.size(0) >= 1 && ext.size(1) == 4,
+              "ext must be contiguous [E, 4] int32");
+  const int64_t E = ext.size(0);
+  TORCH_CHECK(on_dev(ext_off, torch::kInt) && ext_off.numel() == Mt + 1,
+              "ext_off must be contiguous [Mt + 1] int32");
+  TORCH_CHECK(on_dev(sta_off, torch::kInt) && sta_off.numel() == N + 1,
+              "sta_off must be contiguous [N + 1] int32");
+  TORCH_CHECK(on_dev(sta_ent, torch::kInt) && sta_ent.numel() <= 2 * Nbase,
+              "sta_ent must be contiguous int32, at most 2 * Nbase entries");
+  TORCH_CHECK(E < (int64_t(1) << 31) / Nbase && Mt * N < (int64_t(1) << 28),
+              "too many extents or parameters");
+  // the kernels read 2x2 matrices as two 16-byte loads
+  for (const torch::Tensor* t : {&xs, &cohs, &J})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "xs, cohs and J must be 16-byte aligned");
+  LbfgsMfArgs a = {};
+  a.xs = ccptr(xs); a.cohs = ccptr(cohs); a.J = ccptr(J);
+  a.pairs = ip(pairs); a.chunk_tab = ip(chunk_tab);
+  a.ext = ip(ext); a.ext_off = ip(ext_off);
+  a.sta_off = ip(sta_off); a.sta_ent = ip(sta_ent);
+  a.F = (int)F; a.M = (int)M; a.T = (int)T; a.Nbase = (int)Nbase;
+  a.N = (int)N; a.Mt = (int)Mt; a.E = (int)E;
+  a.nu = (float)robust_nu;
+  auto fopts = torch::dtype(torch::kFloat).device(xs.device());
+  auto copts = torch::dtype(torch::kComplexFloat).device(xs.device());
+  auto sres = torch::empty({F, R, 4}, copts);
+  auto slots = torch::empty({E, Nbase, 8}, copts);
+  auto cpart = torch::empty({F * ((R + LBFGS_MF_TB - 1) / LBFGS_MF_TB)},
+                            fopts);
+  auto cost = torch::empty({}, fopts);
+  auto grad = torch::empty({Mt * N * 8}, fopts);
+  CHECK_HIP(launch_lbfgs_mf(a, cptr(sres), cptr(slots),
+                            cpart.data_ptr<float>(), cost.data_ptr<float>(),
+                            grad.data_ptr<float>(), cur_stream()));
+  return {cost, grad};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("jtr_grad", &jtr_grad, "gradient-only accumulation (gfx950)");
+  m.def("lbfgs_cost_grad_channels", &lbfgs_cost_grad_channels,
+        "multi-channel LBFGS cost and gradient (gfx950)", py::arg("xs"),
+        py::arg("cohs"), py::arg("J"), py::arg("chunk_tab"), py::arg("pairs"),
+        py::arg("ext"), py::arg("ext_off"), py::arg("sta_off"),
+        py::arg("sta_ent"), py::arg("robust_nu") = 0.0);
   m.def("chol_solve", &chol_solve, "batched damped Cholesky solve (gfx950)");
   m.def("chol_solve_mw", &chol_solve_mw,
         "multi-workgroup damped Cholesky solve (gfx950)");

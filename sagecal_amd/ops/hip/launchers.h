@@ -105,7 +105,40 @@ struct BeamChannels {
   int Nbase, T, Ktot, Nsta, NE;
 };
 
+// The multi-channel LBFGS cost and gradient (lbfgs_mf.hip). Rows
+// r = t*Nbase + b, R = T*Nbase. The host guarantees pair entries below N
+// (negative: the row adds nothing), chunk ids in 0..Mt-1, and the three
+// index tables as hip_host._lbfgs_tables builds them.
+struct LbfgsMfArgs {
+  const float2* xs;         // [F, R, 4] data
+  const float2* cohs;       // [F, M, R, 4] coherencies
+  const float2* J;          // [Mt, N, 4] packed solutions
+  const int* pairs;         // [Nbase, 2]
+  const int* chunk_tab;     // [M, T] global chunk id, chunk_off[ci] added
+  const int* ext;           // [E, 4] extents (ci, c, t0, t1), sorted by c:
+                            // timeslots t0 <= t < t1 of cluster ci, chunk c
+  const int* ext_off;       // [Mt + 1] extents of chunk c: ext_off[c] <= e
+                            // < ext_off[c + 1]
+  const int* sta_off;       // [N + 1] entries of station s in sta_ent
+  const int* sta_ent;       // 2*b + side for every unflagged pair b and
+                            // side (0: p, 1: q), sorted by station, then b
+  int F, M, T, Nbase, N, Mt, E;
+  float nu;                 // robust nu; <= 0: Gaussian cost
+};
+
 extern "C" {
+
+// Threads per workgroup of k_lbfgs_mf_res and pairs per tile of
+// k_lbfgs_mf_grad.
+#define LBFGS_MF_TB 256
+// cost [1] and grad [Mt*N*8] float32, in the order of view_as_real(J), both
+// fully written. Scratch, contents unspecified on entry and exit: sres
+// [F, R, 4], slots [E, Nbase, 8], cpart [F * ceil(R / LBFGS_MF_TB)].
+// hipErrorInvalidValue: a dimension < 1, F > 65535, Nbase / LBFGS_MF_TB >
+// 65535 or N*32 bytes beyond 64 KB of LDS.
+hipError_t launch_lbfgs_mf(LbfgsMfArgs a, float2* sres, float2* slots,
+                           float* cpart, float* cost, float* grad,
+                           hipStream_t stream);
 
 // out [M, R, 4]: written by launch_predict_coh, added into by
 // launch_shapelet_coh. hipErrorInvalidValue: ejones without pairs or

@@ -6,6 +6,7 @@
 #include "predict_mf.hip"
 #include "shapelet_mf.hip"
 #include "jtj.hip"
+#include "lbfgs_mf.hip"
 #include "cholesky.hip"
 #include "element_beam.hip"
 
@@ -225,6 +226,30 @@ hipError_t launch_jtj_accum(
   hipLaunchKernelGGL(k_jtj_reduce, dim3(N + 1, Mt), dim3(64), 0, stream,
       PD, Pg, Pc, present, pairs, pidx, N, Nbase, npair, grad_only, D, g,
       cost);
+  return hipGetLastError();
+}
+
+// residual pass, gradient pass, fixed-order reduction (lbfgs_mf.hip)
+hipError_t launch_lbfgs_mf(LbfgsMfArgs a, float2* sres, float2* slots,
+                           float* cpart, float* cost, float* grad,
+                           hipStream_t stream) {
+  if (a.F < 1 || a.M < 1 || a.T < 1 || a.Nbase < 1 || a.N < 1 || a.Mt < 1 ||
+      a.E < 1 || a.F > 65535)
+    return hipErrorInvalidValue;
+  const long long R = (long long)a.T * a.Nbase;
+  const long long nblk = (R + LBFGS_MF_TB - 1) / LBFGS_MF_TB;
+  const long long tiles = (a.Nbase + LBFGS_MF_TB - 1) / LBFGS_MF_TB;
+  const size_t lds = (size_t)a.N * 4 * sizeof(float2);
+  if (nblk >= (1LL << 31) || tiles > 65535 || lds > 65536 ||
+      (long long)a.Mt * a.N + 1 >= (1LL << 31))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_lbfgs_mf_res, dim3((unsigned)nblk, a.F),
+                     dim3(LBFGS_MF_TB), 0, stream, a, sres, cpart);
+  hipLaunchKernelGGL(k_lbfgs_mf_grad, dim3(a.E, (unsigned)tiles),
+                     dim3(LBFGS_MF_TB), lds, stream, a, sres, slots);
+  hipLaunchKernelGGL(k_lbfgs_mf_reduce, dim3((unsigned)(a.Mt * a.N + 1)),
+                     dim3(WAVE), 0, stream, a, slots, cpart, nblk * a.F, grad,
+                     cost);
   return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@ complex64 views.
 import math
 import os
 
+import numpy as np
 import torch
 
 from . import dispatch
@@ -983,6 +984,125 @@ def lbfgs_cost_grad(x, cohs, J_packed, chunk_off, nchunks, bb, T, Nbase,
         grad += gci
     g = -2.0 * torch.view_as_real(grad).reshape(-1)
     return cost.to(torch.float32), g
+
+
+LBFGS_TSPLIT = 32    # most timeslots of one extent of k_lbfgs_mf_grad
+_lbfgs_tab_memo = {}  # (kind, table token, version, ...) -> device tables
+
+
+def _table_memo(kind, table, extra, build):
+    """build() once per (kind, table tensor, extra), like _pair_range."""
+    try:
+        key = (kind, dispatch.obj_token(table), table._version) + extra
+    except RuntimeError:                 # inference tensor: no version
+        return build()
+    hit = _lbfgs_tab_memo.get(key)
+    if hit is None:
+        if len(_lbfgs_tab_memo) > 64:
+            _lbfgs_tab_memo.pop(next(iter(_lbfgs_tab_memo)))
+        hit = _lbfgs_tab_memo[key] = build()
+    return hit
+
+
+def _lbfgs_extents(chunk_tab, Mt):
+    """(ext [E, 4], ext_off [Mt + 1]) int32 on chunk_tab's device, the walk
+    plan of k_lbfgs_mf_grad: every cluster's row of chunk_tab [M, T] cut
+    into runs of one chunk id, runs longer than LBFGS_TSPLIT cut into pieces
+    of at most that; one extent (ci, c, t0, t1) per piece, sorted by chunk c
+    (stable: by cluster, then time), and ext_off[c] the first extent of
+    chunk c. Reads the table back, so it is built once per table."""
+    def build():
+        ct = chunk_tab.cpu().numpy()
+        ext = []
+        for ci, row in enumerate(ct):
+            cuts = np.flatnonzero(np.diff(row)) + 1
+            for a, b in zip(np.r_[0, cuts], np.r_[cuts, len(row)]):
+                ext += [(ci, int(row[a]), t0, min(t0 + LBFGS_TSPLIT, int(b)))
+                        for t0 in range(int(a), int(b), LBFGS_TSPLIT)]
+        ext = np.array(ext, dtype=np.int32).reshape(-1, 4)
+        ext = ext[np.argsort(ext[:, 1], kind='stable')]
+        off = np.zeros(Mt + 1, dtype=np.int32)
+        off[1:] = np.cumsum(np.bincount(ext[:, 1], minlength=Mt))
+        return tuple(torch.from_numpy(a).to(chunk_tab.device)
+                     for a in (ext, off))
+    return _table_memo('ext', chunk_tab, (Mt, LBFGS_TSPLIT), build)
+
+
+def _lbfgs_stations(pairs, N):
+    """(sta_off [N + 1], sta_ent) int32 on pairs' device, what
+    k_lbfgs_mf_reduce sums for a station: entry 2*b + side for every pair b
+    without a negative entry and side 0 (p) and 1 (q), sorted by station,
+    then by entry. Reads the table back, so it is built once per table."""
+    def build():
+        pr = pairs.cpu().numpy()
+        ok = np.flatnonzero((pr >= 0).all(axis=1))
+        sta = pr[ok].reshape(-1)                    # p0, q0, p1, q1, ...
+        ent = (2 * ok[:, None] + np.arange(2)).reshape(-1)
+        order = np.argsort(sta, kind='stable')
+        off = np.zeros(N + 1, dtype=np.int32)
+        off[1:] = np.cumsum(np.bincount(sta, minlength=N))
+        return tuple(torch.from_numpy(a).to(pairs.device)
+                     for a in (off, ent[order].astype(np.int32)))
+    return _table_memo('sta', pairs, (N,), build)
+
+
+def lbfgs_cost_grad_channels(xs, cohs, J, chunk_tab, pairs, robust_nu=None):
+    """Cost and gradient of the LBFGS objective summed over the channels,
+    the sum over f of lbfgs_cost_grad(xs[f], cohs[f], ...), in three launches
+    whatever F and M (lbfgs_mf.hip): xs [F, R, 2, 2], cohs [F, M, R, 2, 2],
+    J [Mt, N, 2, 2] complex; chunk_tab [M, T] global chunk id of each
+    (cluster, timeslot), chunk_off[ci] included; pairs [Nbase, 2] stations of
+    the baselines, stored either way round and in any order, R = T * Nbase,
+    a row whose pair has a negative entry adds nothing. Gaussian cost, or
+    with robust_nu sum log1p(e2 / nu). Returns (cost [] float32, grad
+    [Mt*N*8] float32 in the order of view_as_real(J)); bitwise the same from
+    call to call. The first call with a new pair or chunk table reads it
+    back, for the bounds check and the kernels' index tables; after that the
+    path has no host synchronisation."""
+    dev = xs.device
+    if xs.dim() != 4 or tuple(xs.shape[2:]) != (2, 2):
+        raise ValueError(f"xs must be [F, R, 2, 2], got {tuple(xs.shape)}")
+    F, R = int(xs.shape[0]), int(xs.shape[1])
+    if J.dim() != 4 or tuple(J.shape[2:]) != (2, 2) or J.shape[0] < 1 \
+            or J.shape[1] < 1:
+        raise ValueError("J must be [Mt, N, 2, 2]")
+    Mt, N = int(J.shape[0]), int(J.shape[1])
+    if cohs.dim() != 5 or cohs.shape[0] != F \
+            or tuple(cohs.shape[2:]) != (R, 2, 2):
+        raise ValueError(f"cohs must be [{F}, M, {R}, 2, 2], got "
+                         f"{tuple(cohs.shape)}")
+    M = int(cohs.shape[1])
+    if chunk_tab.dim() != 2 or chunk_tab.shape[0] != M:
+        raise ValueError(f"chunk_tab must be [{M}, T]")
+    if pairs.dim() != 2 or pairs.shape[1] != 2 \
+            or chunk_tab.shape[1] * pairs.shape[0] != R:
+        raise ValueError("pairs must be [Nbase, 2] with T * Nbase rows")
+    if robust_nu is not None and not float(robust_nu) > 0.0:
+        raise ValueError("robust_nu must be positive")
+    if F == 0 or R == 0 or M == 0:
+        return (torch.zeros((), dtype=torch.float32, device=dev),
+                torch.zeros(Mt * N * 8, dtype=torch.float32, device=dev))
+    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
+    chunk_tab, pairs = i32(chunk_tab), i32(pairs)
+    # the kernels index J by both tables with no checks of their own
+    if _pair_range(pairs)[1] >= N:
+        raise ValueError(f"pairs name a station outside the {N} of J")
+    lo, hi = _pair_range(chunk_tab)
+    if lo < 0 or hi >= Mt:
+        raise ValueError(f"chunk_tab names chunks {lo}..{hi}, J has {Mt}")
+    ext, ext_off = _lbfgs_extents(chunk_tab, Mt)
+    sta_off, sta_ent = _lbfgs_stations(pairs, N)
+
+    def c64(t, *shape):
+        # contiguous, and 16-byte aligned for the kernels' float4 loads (a
+        # view may start 8 bytes into its storage)
+        t = t.to(torch.complex64).reshape(*shape).contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+    cost, grad = _ext().lbfgs_cost_grad_channels(
+        c64(xs, F, R, 4), c64(cohs, F, M, R, 4), c64(J, Mt, N, 4), chunk_tab,
+        pairs, ext, ext_off, sta_off, sta_ent,
+        0.0 if robust_nu is None else float(robust_nu))
+    return cost, grad
 
 
 _chol_scratch = {}

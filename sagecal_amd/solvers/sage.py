@@ -149,6 +149,15 @@ def _all_channels_ok(pack, t):
             and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
 
 
+def _lbfgs_channels_ok(t):
+    """Whether the fused multi-channel LBFGS kernels
+    (ops.lbfgs_cost_grad_channels) take a cost/gradient on tensor t: device
+    tensors and SAGECAL_LBFGS_CHANNELS=1, which is off by default and which
+    SAGECAL_FORCE_REFERENCE=1 overrides (ops.lbfgs_channels_on reads both,
+    for ops.lbfgs_cost_grad as well)."""
+    return t.is_cuda and ops.lbfgs_channels_on()
+
+
 def _chunk_table(state, T, Nbase, device):
     """[M, T] int32 on `device`: global chunk id (chunk_off included) of
     every (cluster, timeslot), the rows of R.chunk_rows_for one per

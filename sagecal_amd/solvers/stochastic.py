@@ -61,16 +61,27 @@ def _cost_grad_band_multifreq(v, xs, cohs_f, chunk_off, nchunks, bb, T,
     the role of the reference's fused multifreq gradient kernel
     (lbfgs_multifreq.cu:29 kernel_deriv_r_robust / cudakernel_lbfgs_
     multifreq_r_robust, Dirac.h:523-525). xs: [F, B, 2, 2];
-    cohs_f: list of [M, B, 2, 2] per channel."""
+    cohs_f: list of [M, B, 2, 2] per channel, or their stack
+    [F, M, B, 2, 2]. With SAGECAL_LBFGS_CHANNELS=1 on the device the
+    channels go through one ops.lbfgs_cost_grad_channels call."""
     J = torch.view_as_complex(v.reshape(Mt, N, 2, 2, 2).contiguous())
-    cost = None
-    grad = None
-    for fi in range(xs.shape[0]):
-        c, g = ops.lbfgs_cost_grad(xs[fi], cohs_f[fi], J, chunk_off,
-                                   nchunks, bb, T, Nbase,
-                                   robust_nu=robust_nu)
-        cost = c if cost is None else cost + c
-        grad = g if grad is None else grad + g
+    from .sage import _lbfgs_channels_ok
+    if _lbfgs_channels_ok(xs) and xs.shape[1] == T * Nbase:
+        if not torch.is_tensor(cohs_f):
+            cohs_f = torch.stack(list(cohs_f))
+        cost, grad = ops.lbfgs_cost_grad_channels(
+            xs, cohs_f, J,
+            ops.lbfgs_chunk_table(chunk_off, nchunks, T, xs.device),
+            ops.lbfgs_pair_table(bb, Nbase, xs.device), robust_nu)
+    else:
+        cost = None
+        grad = None
+        for fi in range(xs.shape[0]):
+            c, g = ops.lbfgs_cost_grad(xs[fi], cohs_f[fi], J, chunk_off,
+                                       nchunks, bb, T, Nbase,
+                                       robust_nu=robust_nu)
+            cost = c if cost is None else cost + c
+            grad = g if grad is None else grad + g
     if consensus is not None:
         y, bz, rho = consensus
         d = v - bz
@@ -207,14 +218,27 @@ class MinibatchConsensusCalibration:
                             Nbase, fdelta_ch, lbfgs_iters, robust_nu,
                             cons):
         from . import lbfgs as lbfgs_mod
+        from . import sage
         u, v, w = tile.u[rows], tile.v[rows], tile.w[rows]
-        cohs_f = []
-        for fi in range(a, b):
-            c = ops.predict_coh(self.pack, u, v, w,
-                                float(tile.freqs[fi]), tile.freq0,
-                                fdelta_ch, tile.tdelta, tile.dec0)
-            cohs_f.append(c.to(self.dtype))
+        fused = sage._lbfgs_channels_ok(u)
+        if fused and sage._all_channels_ok(self.pack, u):
+            # one launch for the band's coherencies, kept as [F, M, B, 2, 2]
+            cohs_f = ops.predict_coh_channels(
+                self.pack, u, v, w, [float(f) for f in tile.freqs[a:b]],
+                tile.freq0, fdelta_ch, tile.tdelta, tile.dec0,
+                shapelets=True).to(self.dtype)
+        else:
+            cohs_f = []
+            for fi in range(a, b):
+                c = ops.predict_coh(self.pack, u, v, w,
+                                    float(tile.freqs[fi]), tile.freq0,
+                                    fdelta_ch, tile.tdelta, tile.dec0)
+                cohs_f.append(c.to(self.dtype))
+            if fused:
+                cohs_f = torch.stack(cohs_f)
         xs = tile.xo[a:b, rows].to(self.dtype)
+        if fused:
+            xs = xs.contiguous()     # once, not in every evaluation
         Mt, N = band.J.shape[0], band.J.shape[1]
 
         def fg(vv):
