@@ -321,6 +321,90 @@ def lbfgs_cost_grad_channels(xs, cohs, J, chunk_tab, pairs, robust_nu=None):
     return cost, grad.reshape(-1)
 
 
+def joint_kernel_on():
+    """SAGECAL_JOINT_KERNEL=1 opts lm.joint_lm_solve into the kernels of
+    joint_jtj.hip on device tensors; off by default, and
+    SAGECAL_FORCE_REFERENCE=1 overrides it."""
+    return (os.environ.get('SAGECAL_JOINT_KERNEL') == '1'
+            and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
+
+
+def _joint_blocks(chunk_off, nchunks, blocked):
+    """Chunks per cluster Kb of the blocked layout, or None for dense."""
+    if not blocked:
+        return None
+    nchunks = [int(n) for n in nchunks]
+    Kb = nchunks[0]
+    if any(n != Kb for n in nchunks) or \
+            [int(o) for o in chunk_off] != [ci * Kb
+                                            for ci in range(len(nchunks))]:
+        raise ValueError("blocked=True needs the same chunk count in every "
+                         f"cluster, packed in cluster order; got {nchunks}")
+    return Kb
+
+
+def joint_jtj_jtr(x, cohs, J, chunk_off, nchunks, bb, T, Nbase, weights=None,
+                  blocked=False):
+    """(H, g, cost) of the joint cross-cluster Gauss-Newton step,
+    R.joint_jtj_jtr: H [P, P], g [P], cost [] with P = 8 Mt N, parameter
+    order (chunk, station, 8). blocked=True, for the same chunk count Kb in
+    every cluster (else ValueError): chunk k of every cluster covers the
+    same timeslots and the blocks do not couple, so only they are returned,
+    H [Kb, Pb, Pb], g [Kb, Pb], cost [Kb] with Pb = 8 M N and parameter order
+    (cluster, station, 8). On the GPU the two launches of joint_jtj.hip, in
+    float32, where rows r = t*Nbase + b and a pair of bb[:Nbase] with a
+    negative entry adds nothing; elsewhere R.joint_jtj_jtr and, blocked, a
+    gather of its diagonal blocks."""
+    Kb = _joint_blocks(chunk_off, nchunks, blocked)
+    if _use_hip(x):
+        from . import hip_host
+        return hip_host.joint_jtj_jtr(
+            x, cohs, J, lbfgs_chunk_table(chunk_off, nchunks, T, x.device),
+            lbfgs_pair_table(bb, Nbase, x.device), weights, blocked)
+    H, g, _ = R.joint_jtj_jtr(x, cohs, J, chunk_off, nchunks, bb, T, Nbase,
+                              weights)
+    if not blocked:
+        return H, g, _
+    M, N = len(nchunks), int(J.shape[1])
+    # parameter (k; ci, s, i) of block k sits at ((ci*Kb + k)*N + s)*8 + i
+    idx = ((torch.arange(M, device=x.device)[None, :, None] * Kb
+            + torch.arange(Kb, device=x.device)[:, None, None]) * (N * 8)
+           + torch.arange(N * 8, device=x.device)[None, None, :]
+           ).reshape(Kb, -1)
+    Hb = H[idx[:, :, None], idx[:, None, :]]
+    return Hb, g[idx], joint_cost(x, cohs, J, chunk_off, nchunks, bb, T,
+                                  Nbase, weights, blocked=True)
+
+
+def joint_cost(x, cohs, J, chunk_off, nchunks, bb, T, Nbase, weights=None,
+               blocked=False):
+    """The weighted cost of joint_jtj_jtr alone at J, [] or with
+    blocked=True per block [Kb]: the trial cost of the joint LM. On the GPU
+    the cost kernels of joint_jtj.hip, which allocate no H."""
+    Kb = _joint_blocks(chunk_off, nchunks, blocked)
+    if _use_hip(x):
+        from . import hip_host
+        return hip_host.joint_cost(
+            x, cohs, J, lbfgs_chunk_table(chunk_off, nchunks, T, x.device),
+            lbfgs_pair_table(bb, Nbase, x.device), weights, blocked)
+    V = torch.zeros_like(x)
+    for ci in range(len(nchunks)):
+        rows = R.chunk_rows_for(ci, nchunks, T, Nbase, x.shape[0], x.device)
+        V = V + R.apply_jones(
+            cohs[ci], J[chunk_off[ci]:chunk_off[ci] + int(nchunks[ci])], bb,
+            rows)
+    e2 = ((x - V).abs() ** 2).sum(dim=(-1, -2))
+    if weights is not None:
+        e2 = e2 * weights
+    if not blocked:
+        return e2.sum()
+    rows = R.chunk_rows_for(0, nchunks, T, Nbase, x.shape[0], x.device)
+    if rows is None:
+        return e2.sum().unsqueeze(0)
+    return torch.zeros(Kb, dtype=e2.dtype, device=e2.device).index_add_(
+        0, rows, e2)
+
+
 def lbfgs_cost_grad(x, cohs, J_packed, chunk_off, nchunks, bb, T, Nbase,
                     robust_nu=None, weights=None):
     if _use_hip(x) and lbfgs_channels_on() and weights is None \

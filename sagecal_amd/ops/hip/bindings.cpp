@@ -923,8 +923,117 @@ std::vector<torch::Tensor> lbfgs_cost_grad_channels(
   return {cost, grad};
 }
 
+// Joint cross-cluster normal equations (joint_jtj.hip): x [R, 4], cohs
+// [M, R, 4] and J [Mt, N, 4] complex64, optional wts [R] float32, pairs
+// [Nbase, 2] and chunk_tab [M, T] int32 with R == T * Nbase, and the tables
+// of hip_host._joint_tables (pieces, etab, gtab, cbin, sdst, gdst, cpos) and
+// hip_host._lbfgs_stations (sta_off, sta_ent). nblk blocks of Mt / nblk
+// chunks each: returns (H [nblk, ld, ld], g [nblk, ld], cost [nbin]) with
+// ld = 8 N Mt / nblk, or with cost_only (cost [nbin],) at this J. The caller
+// guarantees chunk ids below Mt, pair entries below N and tables that match
+// chunk_tab and pairs.
+std::vector<torch::Tensor> joint_jtj(
+    torch::Tensor x, torch::Tensor cohs, torch::Tensor J,
+    c10::optional<torch::Tensor> wts, torch::Tensor pairs,
+    torch::Tensor chunk_tab, torch::Tensor pieces, torch::Tensor etab,
+    torch::Tensor gtab, torch::Tensor cbin, torch::Tensor sdst,
+    torch::Tensor gdst, torch::Tensor cpos, torch::Tensor sta_off,
+    torch::Tensor sta_ent, int64_t nblk, int64_t nbin, bool cost_only) {
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType ty) {
+    return t.is_cuda() && t.device() == x.device() &&
+           t.scalar_type() == ty && t.is_contiguous();
+  };
+  TORCH_CHECK(on_dev(x, torch::kComplexFloat) && x.dim() == 2 &&
+              x.size(0) >= 1 && x.size(1) == 4,
+              "x must be contiguous [R, 4] complex64 on the device");
+  const int64_t R = x.size(0);
+  TORCH_CHECK(on_dev(cohs, torch::kComplexFloat) && cohs.dim() == 3 &&
+              cohs.size(0) >= 1 && cohs.size(1) == R && cohs.size(2) == 4,
+              "cohs must be contiguous [M, R, 4] complex64");
+  const int64_t M = cohs.size(0);
+  TORCH_CHECK(on_dev(J, torch::kComplexFloat) && J.dim() == 3 &&
+              J.size(0) >= 1 && J.size(1) >= 1 && J.size(2) == 4,
+              "J must be contiguous [Mt, N, 4] complex64");
+  const int64_t Mt = J.size(0), N = J.size(1);
+  TORCH_CHECK(!wts.has_value() ||
+              (on_dev(*wts, torch::kFloat) && wts->numel() == R),
+              "weights must be contiguous [R] float32");
+  TORCH_CHECK(on_dev(chunk_tab, torch::kInt) && chunk_tab.dim() == 2 &&
+              chunk_tab.size(0) == M && chunk_tab.size(1) >= 1,
+              "chunk_tab must be contiguous [M, T] int32");
+  TORCH_CHECK(on_dev(pairs, torch::kInt) && pairs.dim() == 2 &&
+              pairs.size(0) >= 1 && pairs.size(1) == 2,
+              "pairs must be contiguous [Nbase, 2] int32");
+  const int64_t T = chunk_tab.size(1), Nbase = pairs.size(0);
+  TORCH_CHECK(T * Nbase == R && R < (int64_t(1) << 31),
+              "rows must be T * Nbase, below 2^31");
+  TORCH_CHECK(on_dev(pieces, torch::kInt) && pieces.dim() == 2 &&
+              pieces.size(0) >= 1 && pieces.size(1) == 2,
+              "pieces must be contiguous [E, 2] int32");
+  const int64_t E = pieces.size(0), ntri = M * (M + 1) / 2;
+  TORCH_CHECK(on_dev(cbin, torch::kInt) && cbin.numel() == E,
+              "cbin must be contiguous [E] int32");
+  TORCH_CHECK(nblk >= 1 && Mt % nblk == 0 && nbin >= 1,
+              "Mt must be a multiple of the block count");
+  TORCH_CHECK(Mt * N < (int64_t(1) << 27), "too many parameters");
+  for (const torch::Tensor* t : {&x, &cohs, &J})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "x, cohs and J must be 16-byte aligned");
+  JointJtjArgs a = {};
+  a.x = ccptr(x); a.cohs = ccptr(cohs); a.J = ccptr(J);
+  a.wts = wts.has_value() ? wts->data_ptr<float>() : nullptr;
+  a.pairs = ip(pairs); a.chunk_tab = ip(chunk_tab); a.pieces = ip(pieces);
+  a.cbin = ip(cbin);
+  a.M = (int)M; a.T = (int)T; a.Nbase = (int)Nbase; a.N = (int)N;
+  a.Mt = (int)Mt; a.E = (int)E; a.nbin = (int)nbin;
+  a.ld = 8 * N * (Mt / nblk);
+  auto fopts = torch::dtype(torch::kFloat).device(x.device());
+  auto copts = torch::dtype(torch::kComplexFloat).device(x.device());
+  auto PC = torch::empty({Nbase, E}, fopts);
+  auto cost = torch::empty({nbin}, fopts);
+  if (cost_only) {
+    CHECK_HIP(launch_joint_cost(a, PC.data_ptr<float>(),
+                                cost.data_ptr<float>(), cur_stream()));
+    return {cost};
+  }
+  TORCH_CHECK(on_dev(etab, torch::kInt) && etab.numel() == E * ntri,
+              "etab must be contiguous [E, M(M+1)/2] int32");
+  TORCH_CHECK(on_dev(gtab, torch::kInt) && gtab.numel() == E * M,
+              "gtab must be contiguous [E, M] int32");
+  TORCH_CHECK(on_dev(sdst, torch::kInt) && sdst.dim() == 2 &&
+              sdst.size(0) >= 1 && sdst.size(1) == 2,
+              "sdst must be contiguous [D, 2] int32");
+  TORCH_CHECK(on_dev(gdst, torch::kInt) && gdst.numel() >= 1 &&
+              gdst.numel() <= Mt, "gdst must be contiguous [G] int32");
+  TORCH_CHECK(on_dev(cpos, torch::kInt) && cpos.numel() == 2 * Mt,
+              "cpos must be contiguous [Mt, 2] int32");
+  TORCH_CHECK(on_dev(sta_off, torch::kInt) && sta_off.numel() == N + 1,
+              "sta_off must be contiguous [N + 1] int32");
+  TORCH_CHECK(on_dev(sta_ent, torch::kInt) && sta_ent.numel() <= 2 * Nbase,
+              "sta_ent must be contiguous int32, at most 2 * Nbase entries");
+  a.etab = ip(etab); a.gtab = ip(gtab); a.sdst = ip(sdst); a.gdst = ip(gdst);
+  a.cpos = ip(cpos); a.sta_off = ip(sta_off); a.sta_ent = ip(sta_ent);
+  a.D = (int)sdst.size(0); a.G = (int)gdst.numel();
+  auto PE = torch::empty({Nbase, (int64_t)a.D, 2, 4}, copts);
+  auto PG = torch::empty({Nbase, (int64_t)a.G, 2, 4}, copts);
+  auto H = torch::zeros({nblk, (int64_t)a.ld, (int64_t)a.ld}, fopts);
+  auto g = torch::zeros({nblk, (int64_t)a.ld}, fopts);
+  CHECK_HIP(launch_joint_jtj(a, cptr(PE), cptr(PG), PC.data_ptr<float>(),
+                             H.data_ptr<float>(), g.data_ptr<float>(),
+                             cost.data_ptr<float>(), cur_stream()));
+  return {H, g, cost};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("jtr_grad", &jtr_grad, "gradient-only accumulation (gfx950)");
+  m.attr("JOINT_JTJ_TT") = JOINT_JTJ_TT;
+  m.def("joint_jtj", &joint_jtj,
+        "joint cross-cluster normal equations (gfx950)", py::arg("x"),
+        py::arg("cohs"), py::arg("J"), py::arg("wts"), py::arg("pairs"),
+        py::arg("chunk_tab"), py::arg("pieces"), py::arg("etab"),
+        py::arg("gtab"), py::arg("cbin"), py::arg("sdst"), py::arg("gdst"),
+        py::arg("cpos"), py::arg("sta_off"), py::arg("sta_ent"),
+        py::arg("nblk"), py::arg("nbin"), py::arg("cost_only") = false);
   m.def("lbfgs_cost_grad_channels", &lbfgs_cost_grad_channels,
         "multi-channel LBFGS cost and gradient (gfx950)", py::arg("xs"),
         py::arg("cohs"), py::arg("J"), py::arg("chunk_tab"), py::arg("pairs"),

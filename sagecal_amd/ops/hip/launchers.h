@@ -126,7 +126,52 @@ struct LbfgsMfArgs {
   float nu;                 // robust nu; <= 0: Gaussian cost
 };
 
+// The joint cross-cluster normal equations (joint_jtj.hip). Rows
+// r = t*Nbase + b, R = T*Nbase. The host guarantees pair entries below N
+// (negative: the pair adds nothing), chunk ids in 0..Mt-1 and the tables
+// as hip_host._joint_tables and hip_host._lbfgs_stations build them.
+struct JointJtjArgs {
+  const float2* x;          // [R, 4] data
+  const float2* cohs;       // [M, R, 4] coherencies
+  const float2* J;          // [Mt, N, 4] packed solutions
+  const float* wts;         // [R] row weights >= 0, or null
+  const int* pairs;         // [Nbase, 2]
+  const int* chunk_tab;     // [M, T] global chunk id, chunk_off[ci] added
+  const int* pieces;        // [E, 2] timeslots t0 <= t < t1, at most
+                            // JOINT_JTJ_TT of them, every cluster's chunk
+                            // id constant inside; in time order
+  const int* etab;          // [E, M(M+1)/2] 2*slot + first, per piece and
+                            // (ci <= cj) in row-major triangle order
+  const int* gtab;          // [E, M] 2*gslot + first, per piece and cluster
+  const int* cbin;          // [E] cost bin of the piece
+  const int* sdst;          // [D, 2] chunks (c_i, c_j) of slot
+  const int* gdst;          // [G] chunk of gslot
+  const int* cpos;          // [Mt, 2] (block, position in block) of chunk
+  const int* sta_off;       // [N + 1] entries of station s in sta_ent
+  const int* sta_ent;       // 2*b + side, as in LbfgsMfArgs
+  int M, T, Nbase, N, Mt, E, D, G, nbin;
+  long long ld;             // rows of one block of H: 8 N (chunks per block)
+};
+
 extern "C" {
+
+// Threads per workgroup of k_joint_gram, and the most timeslots of one of
+// its pieces (the time tile z is staged for in LDS).
+#define JOINT_JTJ_TB 128
+#define JOINT_JTJ_TT 32
+// H [nblk, ld, ld] and g [nblk, ld] arrive zeroed and get every
+// structurally non-zero entry; cost [nbin] is fully written. Scratch,
+// contents unspecified on entry and exit: PE [Nbase, D, 2, 4], PG
+// [Nbase, G, 2, 4], PC [Nbase, E]. hipErrorInvalidValue: a dimension < 1,
+// 2 M > JOINT_JTJ_TB, or the time tile of M clusters beyond 64 KB of LDS
+// (M > 30).
+hipError_t launch_joint_jtj(JointJtjArgs a, float2* PE, float2* PG, float* PC,
+                            float* H, float* g, float* cost,
+                            hipStream_t stream);
+// cost [nbin] alone, at the J of a; etab, gtab, sdst, gdst, cpos, sta_off
+// and sta_ent are not read, and there is no H to touch.
+hipError_t launch_joint_cost(JointJtjArgs a, float* PC, float* cost,
+                             hipStream_t stream);
 
 // Threads per workgroup of k_lbfgs_mf_res and pairs per tile of
 // k_lbfgs_mf_grad.

@@ -7,6 +7,7 @@
 #include "shapelet_mf.hip"
 #include "jtj.hip"
 #include "lbfgs_mf.hip"
+#include "joint_jtj.hip"
 #include "cholesky.hip"
 #include "element_beam.hip"
 
@@ -250,6 +251,43 @@ hipError_t launch_lbfgs_mf(LbfgsMfArgs a, float2* sres, float2* slots,
   hipLaunchKernelGGL(k_lbfgs_mf_reduce, dim3((unsigned)(a.Mt * a.N + 1)),
                      dim3(WAVE), 0, stream, a, slots, cpart, nblk * a.F, grad,
                      cost);
+  return hipGetLastError();
+}
+
+// LDS of k_joint_gram and k_joint_cost: z, res and the 2 M Jones in play
+static bool joint_shape_ok(const JointJtjArgs& a, size_t* lds) {
+  if (a.M < 1 || a.T < 1 || a.Nbase < 1 || a.N < 1 || a.Mt < 1 || a.E < 1 ||
+      a.nbin < 1 || 2 * a.M > JOINT_JTJ_TB)
+    return false;
+  *lds = ((size_t)JOINT_JTJ_TT * a.M * 8 + JOINT_JTJ_TT * 4 +
+          (size_t)2 * a.M * 4) * sizeof(float2);
+  return *lds <= 65536;
+}
+
+// per-pair pass, then the fixed-order per-station reduction (joint_jtj.hip)
+hipError_t launch_joint_jtj(JointJtjArgs a, float2* PE, float2* PG, float* PC,
+                            float* H, float* g, float* cost,
+                            hipStream_t stream) {
+  size_t lds;
+  if (!joint_shape_ok(a, &lds) || a.D < 1 || a.G < 1 || a.ld < 8)
+    return hipErrorInvalidValue;
+  const long long nred = (long long)a.N * (a.D + a.G) + a.nbin;
+  if (nred >= (1LL << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_joint_gram, dim3(a.Nbase), dim3(JOINT_JTJ_TB), lds,
+                     stream, a, H, PE, PG, PC);
+  hipLaunchKernelGGL(k_joint_reduce, dim3((unsigned)nred), dim3(WAVE), 0,
+                     stream, a, PE, PG, PC, H, g, cost);
+  return hipGetLastError();
+}
+
+hipError_t launch_joint_cost(JointJtjArgs a, float* PC, float* cost,
+                             hipStream_t stream) {
+  size_t lds;
+  if (!joint_shape_ok(a, &lds)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_joint_cost, dim3(a.Nbase), dim3(JOINT_JTJ_TB), lds,
+                     stream, a, PC);
+  hipLaunchKernelGGL(k_joint_cost_reduce, dim3(a.nbin), dim3(WAVE), 0, stream,
+                     a, PC, cost);
   return hipGetLastError();
 }
 

@@ -1105,6 +1105,137 @@ def lbfgs_cost_grad_channels(xs, cohs, J, chunk_tab, pairs, robust_nu=None):
     return cost, grad
 
 
+JOINT_TT = 32        # time tile of k_joint_gram (JOINT_JTJ_TT, launchers.h)
+
+
+def _joint_tables(chunk_tab, Mt, blocked):
+    """The walk plan of k_joint_gram and the destinations of k_joint_reduce,
+    int32 on chunk_tab's device, as the dict JointJtjArgs is filled from:
+    pieces [E, 2] (the finest segments over which every cluster's chunk id
+    is constant, cut at JOINT_TT timeslots, in time order), etab
+    [E, M(M+1)/2] and gtab [E, M] (2*slot + first: the slot a piece adds
+    to and whether it is the first to), cbin [E], sdst [D, 2], gdst [G],
+    cpos [Mt, 2], with nblk and nbin. Blocked: chunk c is chunk c % Kb of
+    cluster c // Kb, Kb = Mt / M, and block k holds chunk k of every
+    cluster; ValueError where a timeslot mixes blocks. Reads the table
+    back, so it is built once per table."""
+    def build():
+        ct = chunk_tab.cpu().numpy()
+        M, T = ct.shape
+        Kb = Mt // M
+        if blocked:
+            if Kb * M != Mt or (ct // Kb != np.arange(M)[:, None]).any() \
+                    or (ct % Kb != ct[:1] % Kb).any():
+                raise ValueError(
+                    "the blocked layout needs the same chunk count and "
+                    "chunk boundaries in every cluster")
+            c = np.arange(Mt)
+            cpos = np.stack([c % Kb, c // Kb], axis=1)
+        else:
+            cpos = np.stack([np.zeros(Mt, dtype=np.int64), np.arange(Mt)],
+                            axis=1)
+        cuts = np.flatnonzero((np.diff(ct, axis=1) != 0).any(axis=0)) + 1
+        pieces = [(t0, min(t0 + JOINT_TT, int(b)))
+                  for a, b in zip(np.r_[0, cuts], np.r_[cuts, T])
+                  for t0 in range(int(a), int(b), JOINT_TT)]
+        slots, gslots, etab, gtab = {}, {}, [], []
+
+        def slot_of(table, key):
+            first = key not in table
+            return 2 * table.setdefault(key, len(table)) + first
+        for t0, _ in pieces:
+            col = [int(v) for v in ct[:, t0]]
+            etab.append([slot_of(slots, (col[i], col[j]))
+                         for i in range(M) for j in range(i, M)])
+            gtab.append([slot_of(gslots, v) for v in col])
+        cbin = [int(ct[0, t0]) % Kb if blocked else 0 for t0, _ in pieces]
+        tabs = dict(pieces=pieces, etab=etab, gtab=gtab, cbin=cbin,
+                    sdst=list(slots), gdst=list(gslots), cpos=cpos)
+        out = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.int32))
+               .to(chunk_tab.device) for k, v in tabs.items()}
+        out['nblk'] = out['nbin'] = Kb if blocked else 1
+        return out
+    return _table_memo('joint', chunk_tab, (Mt, bool(blocked), JOINT_TT),
+                       build)
+
+
+def _joint_launch(x, cohs, J, chunk_tab, pairs, weights, blocked, cost_only):
+    """Checks and launch shared by joint_jtj_jtr and joint_cost."""
+    dev = x.device
+    if x.dim() != 3 or tuple(x.shape[1:]) != (2, 2):
+        raise ValueError(f"x must be [R, 2, 2], got {tuple(x.shape)}")
+    R = int(x.shape[0])
+    if J.dim() != 4 or tuple(J.shape[2:]) != (2, 2) or J.shape[0] < 1 \
+            or J.shape[1] < 1:
+        raise ValueError("J must be [Mt, N, 2, 2]")
+    Mt, N = int(J.shape[0]), int(J.shape[1])
+    if cohs.dim() != 4 or cohs.shape[0] < 1 \
+            or tuple(cohs.shape[1:]) != (R, 2, 2):
+        raise ValueError(f"cohs must be [M, {R}, 2, 2], got "
+                         f"{tuple(cohs.shape)}")
+    M = int(cohs.shape[0])
+    if chunk_tab.dim() != 2 or chunk_tab.shape[0] != M:
+        raise ValueError(f"chunk_tab must be [{M}, T]")
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or R == 0 \
+            or chunk_tab.shape[1] * pairs.shape[0] != R:
+        raise ValueError("pairs must be [Nbase, 2] with T * Nbase rows")
+    if weights is not None and tuple(weights.shape) != (R,):
+        raise ValueError(f"weights must be [{R}]")
+    if M > 30:
+        raise ValueError("the joint kernels stage 32 timeslots of all "
+                         f"clusters in LDS, at most 30 clusters; got {M}")
+    if _ext().JOINT_JTJ_TT != JOINT_TT:
+        raise RuntimeError("JOINT_TT differs from the kernels' time tile")
+    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
+    chunk_tab, pairs = i32(chunk_tab), i32(pairs)
+    # the kernels index J by both tables with no checks of their own
+    if _pair_range(pairs)[1] >= N:
+        raise ValueError(f"pairs name a station outside the {N} of J")
+    lo, hi = _pair_range(chunk_tab)
+    if lo < 0 or hi >= Mt:
+        raise ValueError(f"chunk_tab names chunks {lo}..{hi}, J has {Mt}")
+    tb = _joint_tables(chunk_tab, Mt, blocked)
+    sta_off, sta_ent = _lbfgs_stations(pairs, N)
+
+    def c64(t, *shape):
+        t = t.to(torch.complex64).reshape(*shape).contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+    if weights is not None:
+        weights = weights.to(device=dev, dtype=torch.float32).contiguous()
+    return _ext().joint_jtj(
+        c64(x, R, 4), c64(cohs, M, R, 4), c64(J, Mt, N, 4), weights, pairs,
+        chunk_tab, tb['pieces'], tb['etab'], tb['gtab'], tb['cbin'],
+        tb['sdst'], tb['gdst'], tb['cpos'], sta_off, sta_ent, tb['nblk'],
+        tb['nbin'], cost_only)
+
+
+def joint_jtj_jtr(x, cohs, J, chunk_tab, pairs, weights=None, blocked=False):
+    """reference.joint_jtj_jtr from the kernels of joint_jtj.hip, two
+    launches: x [R, 2, 2], cohs [M, R, 2, 2], J [Mt, N, 2, 2] complex;
+    chunk_tab [M, T] global chunk id of each (cluster, timeslot); pairs
+    [Nbase, 2] in any order and orientation, R = T * Nbase, a pair with a
+    negative entry adds nothing; weights [R] >= 0 or None. Returns float32
+    (H [P, P], g [P], cost []) with P = 8 Mt N, or with blocked=True
+    (H [Kb, Pb, Pb], g [Kb, Pb], cost [Kb]), Pb = 8 M N, parameter order
+    (cluster, station, 8) inside block k, which holds chunk k of every
+    cluster. H is symmetric bit for bit and all three repeat bit for bit
+    from call to call. The first call with a new pair or chunk table reads
+    it back; after that the path has no host synchronisation."""
+    H, g, cost = _joint_launch(x, cohs, J, chunk_tab, pairs, weights,
+                               blocked, False)
+    if blocked:
+        return H, g, cost
+    return H[0], g[0], cost[0]
+
+
+def joint_cost(x, cohs, J, chunk_tab, pairs, weights=None, blocked=False):
+    """The weighted cost of joint_jtj_jtr alone at J, [] or per block [Kb]:
+    the LM trial cost. No H is allocated or written."""
+    cost, = _joint_launch(x, cohs, J, chunk_tab, pairs, weights, blocked,
+                          True)
+    return cost if blocked else cost[0]
+
+
 _chol_scratch = {}
 
 

@@ -265,7 +265,12 @@ def joint_lm_solve(x, cohs, J_packed, chunk_off, nchunks, bb, T, Nbase,
     The reference polishes jointly only via LBFGS (lmfit.c:1019); a full
     joint LM converges quadratically near the solution and its JtJ/Cholesky
     are batched-GEMM shaped — cheap on MI355X. Used as the refinement stage
-    after SAGE EM sweeps."""
+    after SAGE EM sweeps.
+
+    SAGECAL_JOINT_KERNEL=1 on device tensors: the normal equations and the
+    trial cost come from the kernels of joint_jtj.hip (ops.joint_jtj_jtr,
+    ops.joint_cost), and with the same chunk count K > 1 in every cluster
+    the K uncoupled blocks run as one batched LM (_joint_lm_blocked)."""
     from ..ops import reference as R
     J = J_packed.clone()
     dev = x.device
@@ -274,8 +279,24 @@ def joint_lm_solve(x, cohs, J_packed, chunk_off, nchunks, bb, T, Nbase,
     P = 8 * Mt * N
     mu = None
     nu = 2.0
+    kernels = x.is_cuda and ops.joint_kernel_on()
+    if kernels:
+        ncs = [int(n) for n in nchunks]
+        if ncs[0] > 1 and all(n == ncs[0] for n in ncs):
+            return _joint_lm_blocked(x, cohs, J, chunk_off, nchunks, bb, T,
+                                     Nbase, maxiter, tau, weights)
+
+    def assemble(Jc):
+        if kernels:
+            return ops.joint_jtj_jtr(x, cohs, Jc, chunk_off, nchunks, bb, T,
+                                     Nbase, weights)
+        return R.joint_jtj_jtr(x, cohs, Jc, chunk_off, nchunks, bb, T, Nbase,
+                               weights)
 
     def cost_of(Jc):
+        if kernels:
+            return float(ops.joint_cost(x, cohs, Jc, chunk_off, nchunks, bb,
+                                        T, Nbase, weights))
         V = torch.zeros_like(x)
         for ci in range(len(nchunks)):
             rows = R.chunk_rows_for(ci, nchunks, T, Nbase, x.shape[0], dev)
@@ -290,8 +311,7 @@ def joint_lm_solve(x, cohs, J_packed, chunk_off, nchunks, bb, T, Nbase,
             e2 = e2 * weights
         return float(e2.sum())
 
-    H, g, cost = R.joint_jtj_jtr(x, cohs, J, chunk_off, nchunks, bb, T,
-                                 Nbase, weights)
+    H, g, cost = assemble(J)
     cost = float(cost)
     eye = torch.eye(P, dtype=rdt, device=dev)
     for it in range(maxiter):
@@ -317,14 +337,65 @@ def joint_lm_solve(x, cohs, J_packed, chunk_off, nchunks, bb, T, Nbase,
             nu = 2.0
             if float(dp.norm()) < eps2 * (float(torch.view_as_real(J).norm()) + eps2):
                 break
-            H, g, _ = R.joint_jtj_jtr(x, cohs, J, chunk_off, nchunks, bb, T,
-                                      Nbase, weights)
+            H, g, _ = assemble(J)
         else:
             mu *= nu
             nu *= 2.0
             if nu > 1e12:
                 break
     return J, cost
+
+
+def _joint_lm_blocked(x, cohs, J, chunk_off, nchunks, bb, T, Nbase, maxiter,
+                      tau, weights):
+    """joint_lm_solve for K = nchunks[ci] > 1 chunks in every cluster on the
+    blocked output of the joint kernels: chunk k of every cluster covers the
+    same timeslots, so H is K uncoupled blocks of Pb = 8 M N, and they run
+    as one batched LM as in _lm_solve_eager: per-block mu, gain ratio and
+    accept mask, rejected blocks held with torch.where, no host reads inside
+    the loop. Blocks are independent problems; against the scalar loop only
+    the damping differs, one mu per block instead of one for all."""
+    from ..ops.hip_host import chol_solve_damped
+    M, K = len(nchunks), int(nchunks[0])
+    N = J.shape[1]
+    Pb = 8 * M * N
+    args = (chunk_off, nchunks, bb, T, Nbase, weights)
+
+    def step_to_jones(dp):
+        # block k, order (cluster, station, 8) -> chunk ci*K + k of J
+        d = dp.reshape(K, M, N, 2, 2, 2).transpose(0, 1)
+        return torch.view_as_complex(d.reshape(M * K, N, 2, 2, 2).contiguous())
+
+    def per_chunk(v):                       # [K] -> [M*K, 1, 1, 1]
+        return v.repeat(M)[:, None, None, None]
+
+    H, g, cost = ops.joint_jtj_jtr(x, cohs, J, *args, blocked=True)
+    mu = tau * H.diagonal(dim1=-2, dim2=-1).max(dim=-1).values
+    nu = torch.full_like(mu, 2.0)
+    for it in range(maxiter):
+        if Pb <= 4096:                      # the Cholesky kernels' limit
+            dp = chol_solve_damped(H, g, mu)
+        else:
+            # H is rebuilt before its next use. One block at a time, the
+            # single-matrix solver the scalar loop uses: torch's batched
+            # Cholesky of [16, 5120, 5120] ended in a launch failure on
+            # the MI355X
+            H.diagonal(dim1=-2, dim2=-1).add_(mu[:, None])
+            dp = torch.stack([_chol_solve(H[k], g[k]) for k in range(K)])
+        dp = torch.nan_to_num(dp, nan=0.0, posinf=0.0, neginf=0.0)
+        Jn = J + step_to_jones(dp)
+        cn = ops.joint_cost(x, cohs, Jn, *args, blocked=True)
+        denom = (dp * (mu[:, None] * dp + g)).sum(dim=-1).clamp_min(1e-30)
+        rho = (cost - cn) / denom
+        accept = rho > 0
+        J = torch.where(per_chunk(accept), Jn, J)
+        cost = torch.where(accept, cn, cost)
+        fac = (1.0 - (2.0 * rho - 1.0) ** 3).clamp_min(1.0 / 3.0)
+        mu = torch.where(accept, mu * fac, mu * nu)
+        nu = torch.where(accept, torch.full_like(nu, 2.0), nu * 2.0)
+        if it + 1 < maxiter:
+            H, g, _ = ops.joint_jtj_jtr(x, cohs, J, *args, blocked=True)
+    return J, float(cost.sum())
 
 
 def _lm_body(x, coh, bb, N, nchunk, chunk_rows, weights, layout, J0,
