@@ -329,6 +329,38 @@ def joint_kernel_on():
             and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
 
 
+def rtr_kernel_on():
+    """SAGECAL_RTR_KERNEL=1 opts rtr.rtr_solve and rtr.rtr_solve_graphed
+    into the one-launch inner solve of rtr_tcg.hip on device tensors; off by
+    default, and SAGECAL_FORCE_REFERENCE=1 overrides it."""
+    return (os.environ.get('SAGECAL_RTR_KERNEL') == '1'
+            and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
+
+
+def rtr_tcg(JtJ, Jtr, J, iw, delta, maxit=12, kappa=0.01):
+    """The inner solve of one RTR outer iteration at J [n, N, 2, 2], from
+    the normal equations JtJ [n, 8N, 8N], Jtr [n, 8N] in reference.vecR
+    order, the station scale iw [N] and the radius delta [n]: returns
+    (g, eta, Heta, stats) with g the Riemannian gradient, eta the truncated-CG
+    step, Heta = hess_vec(J, eta), each [n, N, 2, 2], and stats [n, 4] =
+    (<g,g>, <g,eta>, <eta,Heta>, CG iterations entered) in the metric
+    2 Re tr(a^H b). On the GPU one launch of k_rtr_tcg (rtr_tcg.hip), in
+    float32; elsewhere the torch code of solvers.rtr in the input
+    precision."""
+    if _use_hip(J):
+        from . import hip_host
+        return hip_host.rtr_tcg(JtJ, Jtr, J, iw, delta, maxit, kappa)
+    from ..solvers import rtr
+    obj = rtr._Objective(None, iw)
+    obj.JtJ, obj.Jtr = JtJ, Jtr
+    g = obj.grad(J)
+    eta, nit = rtr._tcg_fixed(obj, J, g, delta, maxit, kappa, count=True)
+    Heta = obj.hess_vec(J, eta)
+    stats = torch.stack([rtr._inner(g, g), rtr._inner(g, eta),
+                         rtr._inner(eta, Heta), nit], dim=-1)
+    return g, eta, Heta, stats
+
+
 def _joint_blocks(chunk_off, nchunks, blocked):
     """Chunks per cluster Kb of the blocked layout, or None for dense."""
     if not blocked:

@@ -1024,8 +1024,54 @@ std::vector<torch::Tensor> joint_jtj(
   return {H, g, cost};
 }
 
+// The RTR truncated-CG inner solve (rtr_tcg.hip): JtJ [n, P, P], Jtr [n, P],
+// iw [N] and delta [n] float32, J [n, N, 2, 2] complex64, P = 8 N. Returns
+// (g, eta, Heta [n, N, 2, 2] complex64, stats [n, 4] float32).
+std::vector<torch::Tensor> rtr_tcg(
+    torch::Tensor JtJ, torch::Tensor Jtr, torch::Tensor J, torch::Tensor iw,
+    torch::Tensor delta, int64_t maxit, double kappa) {
+  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType ty) {
+    return t.is_cuda() && t.device() == JtJ.device() &&
+           t.scalar_type() == ty && t.is_contiguous();
+  };
+  TORCH_CHECK(on_dev(J, torch::kComplexFloat) && J.dim() == 4 &&
+              J.size(0) >= 1 && J.size(2) == 2 && J.size(3) == 2,
+              "J must be contiguous [n, N, 2, 2] complex64 on the device");
+  const int64_t n = J.size(0), N = J.size(1), P = 8 * N;
+  TORCH_CHECK(N >= 2 && P <= RTR_TCG_MAXP && n < (int64_t(1) << 31),
+              "rtr_tcg takes 2 <= N <= ", RTR_TCG_MAXP / 8, " stations");
+  TORCH_CHECK(on_dev(JtJ, torch::kFloat) && JtJ.dim() == 3 &&
+              JtJ.size(0) == n && JtJ.size(1) == P && JtJ.size(2) == P,
+              "JtJ must be contiguous [n, 8N, 8N] float32");
+  TORCH_CHECK(on_dev(Jtr, torch::kFloat) && Jtr.dim() == 2 &&
+              Jtr.size(0) == n && Jtr.size(1) == P,
+              "Jtr must be contiguous [n, 8N] float32");
+  TORCH_CHECK(on_dev(iw, torch::kFloat) && iw.dim() == 1 && iw.size(0) == N,
+              "iw must be contiguous [N] float32");
+  TORCH_CHECK(on_dev(delta, torch::kFloat) && delta.dim() == 1 &&
+              delta.size(0) == n, "delta must be contiguous [n] float32");
+  TORCH_CHECK(maxit >= 0 && maxit < (int64_t(1) << 24),
+              "maxit must be in 0 .. 2^24");
+  for (const torch::Tensor* t : {&JtJ, &Jtr, &J})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "JtJ, Jtr and J must be 16-byte aligned");
+  RtrTcgArgs a = {};
+  a.JtJ = fp(JtJ); a.Jtr = fp(Jtr); a.J = ccptr(J); a.iw = fp(iw);
+  a.delta = fp(delta);
+  a.n = (int)n; a.N = (int)N; a.maxit = (int)maxit; a.kappa = (float)kappa;
+  auto g = torch::empty_like(J), eta = torch::empty_like(J),
+       Heta = torch::empty_like(J);
+  auto stats = torch::empty({n, 4}, JtJ.options());
+  CHECK_HIP(launch_rtr_tcg(a, cptr(g), cptr(eta), cptr(Heta),
+                           stats.data_ptr<float>(), cur_stream()));
+  return {g, eta, Heta, stats};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("jtr_grad", &jtr_grad, "gradient-only accumulation (gfx950)");
+  m.def("rtr_tcg", &rtr_tcg, "RTR truncated-CG inner solve (gfx950)",
+        py::arg("JtJ"), py::arg("Jtr"), py::arg("J"), py::arg("iw"),
+        py::arg("delta"), py::arg("maxit"), py::arg("kappa"));
   m.attr("JOINT_JTJ_TT") = JOINT_JTJ_TT;
   m.def("joint_jtj", &joint_jtj,
         "joint cross-cluster normal equations (gfx950)", py::arg("x"),

@@ -153,7 +153,29 @@ struct JointJtjArgs {
   long long ld;             // rows of one block of H: 8 N (chunks per block)
 };
 
+// The RTR truncated-CG inner solve (rtr_tcg.hip), one workgroup per chunk.
+// P = 8 N parameters per chunk in reference.vecR order.
+struct RtrTcgArgs {
+  const float* JtJ;         // [n, P, P], read as symmetric
+  const float* Jtr;         // [n, P]
+  const float2* J;          // [n, N, 4]
+  const float* iw;          // [N] per-station gradient scale
+  const float* delta;       // [n] trust-region radius
+  int n, N, maxit;
+  float kappa;
+};
+
 extern "C" {
+
+// Threads per workgroup of k_rtr_tcg and the most parameters of a chunk:
+// a thread owns one float4 of every vector.
+#define RTR_TCG_TB 1024
+#define RTR_TCG_MAXP 4096
+// g, eta, Heta [n, N, 4] and stats [n, 4] (<g,g>, <g,eta>, <eta,Heta>, CG
+// iterations entered), all fully written. hipErrorInvalidValue: n < 1,
+// N < 2, 8 N > RTR_TCG_MAXP or maxit < 0.
+hipError_t launch_rtr_tcg(RtrTcgArgs a, float2* g, float2* eta, float2* Heta,
+                          float* stats, hipStream_t stream);
 
 // Threads per workgroup of k_joint_gram, and the most timeslots of one of
 // its pieces (the time tile z is staged for in LDS).

@@ -8,6 +8,7 @@
 #include "jtj.hip"
 #include "lbfgs_mf.hip"
 #include "joint_jtj.hip"
+#include "rtr_tcg.hip"
 #include "cholesky.hip"
 #include "element_beam.hip"
 
@@ -288,6 +289,17 @@ hipError_t launch_joint_cost(JointJtjArgs a, float* PC, float* cost,
                      stream, a, PC);
   hipLaunchKernelGGL(k_joint_cost_reduce, dim3(a.nbin), dim3(WAVE), 0, stream,
                      a, PC, cost);
+  return hipGetLastError();
+}
+
+// one workgroup per chunk; LDS holds v, Hv and iw (rtr_tcg.hip)
+hipError_t launch_rtr_tcg(RtrTcgArgs a, float2* g, float2* eta, float2* Heta,
+                          float* stats, hipStream_t stream) {
+  if (a.n < 1 || a.N < 2 || 8 * (long long)a.N > RTR_TCG_MAXP || a.maxit < 0)
+    return hipErrorInvalidValue;
+  const size_t lds = (size_t)(2 * 8 * a.N + a.N) * sizeof(float);
+  hipLaunchKernelGGL(k_rtr_tcg, dim3(a.n), dim3(RTR_TCG_TB), lds, stream, a,
+                     g, eta, Heta, stats);
   return hipGetLastError();
 }
 

@@ -1236,6 +1236,38 @@ def joint_cost(x, cohs, J, chunk_tab, pairs, weights=None, blocked=False):
     return cost if blocked else cost[0]
 
 
+RTR_TCG_MAXN = 512          # RTR_TCG_MAXP / 8 of launchers.h
+
+
+def rtr_tcg(JtJ, Jtr, J, iw, delta, maxit=12, kappa=0.01):
+    """The RTR inner solve of one outer iteration in one launch of k_rtr_tcg
+    (rtr_tcg.hip), one workgroup per chunk: JtJ [n, 8N, 8N], Jtr [n, 8N],
+    J [n, N, 2, 2], iw [N], delta [n] on the device, computed in float32.
+    Returns (g, eta, Heta) [n, N, 2, 2] complex64, what rtr._Objective.grad,
+    rtr._tcg_fixed and hess_vec(J, eta) give, and stats [n, 4] float32 =
+    (<g,g>, <g,eta>, <eta,Heta>, CG iterations entered). Two calls on the
+    same input agree bit for bit; no host synchronisation."""
+    if J.dim() != 4 or tuple(J.shape[2:]) != (2, 2) or J.shape[0] < 1:
+        raise ValueError(f"J must be [n, N, 2, 2], got {tuple(J.shape)}")
+    n, N = int(J.shape[0]), int(J.shape[1])
+    if N < 2 or N > RTR_TCG_MAXN:
+        raise ValueError(f"rtr_tcg takes 2 to {RTR_TCG_MAXN} stations "
+                         f"(8 N <= {8 * RTR_TCG_MAXN}), got {N}")
+    if tuple(JtJ.shape) != (n, 8 * N, 8 * N) \
+            or tuple(Jtr.shape) != (n, 8 * N):
+        raise ValueError(f"JtJ must be [{n}, {8 * N}, {8 * N}] and Jtr "
+                         f"[{n}, {8 * N}]")
+    if tuple(iw.shape) != (N,) or tuple(delta.shape) != (n,):
+        raise ValueError(f"iw must be [{N}] and delta [{n}]")
+    if int(maxit) < 0:
+        raise ValueError("maxit must not be negative")
+    dev = J.device
+    f32 = lambda t: t.to(device=dev, dtype=torch.float32).contiguous()
+    return tuple(_ext().rtr_tcg(f32(JtJ), f32(Jtr),
+                                J.to(torch.complex64).contiguous(), f32(iw),
+                                f32(delta), int(maxit), float(kappa)))
+
+
 _chol_scratch = {}
 
 

@@ -214,13 +214,18 @@ def rtr_solve(prob, J0, maxiter=20, rsd_iters=2, delta0=None,
     else:
         delta = torch.full((n,), delta0, dtype=gnorm.dtype, device=dev)
     delta_bar = delta * 8
+    kern = _use_kernel(J)
     for it in range(maxiter):
-        eta = _tcg(obj, J, g, delta)
+        if kern:
+            eta, mdec = _kernel_step(obj, J, delta, 30)   # _tcg's maxit
+        else:
+            eta = _tcg(obj, J, g, delta)
         Jn = J + eta          # identity retraction (fns_R)
         cn = obj.cost(Jn)
-        # model decrease m(0) - m(eta)
-        Heta = obj.hess_vec(J, eta)
-        mdec = -(_inner(g, eta) + 0.5 * _inner(eta, Heta))
+        if not kern:
+            # model decrease m(0) - m(eta)
+            Heta = obj.hess_vec(J, eta)
+            mdec = -(_inner(g, eta) + 0.5 * _inner(eta, Heta))
         rho = (cost - cn) / mdec.clamp_min(1e-30)
         accept = (rho > 0.1) & (cn < cost)
         J = torch.where(accept[:, None, None, None], Jn, J)
@@ -230,6 +235,8 @@ def rtr_solve(prob, J0, maxiter=20, rsd_iters=2, delta0=None,
                                         torch.minimum(delta * 2.0,
                                                       delta_bar), delta))
         obj.refresh(J)
+        if kern:
+            continue          # the kernel forms the gradient itself; no poll
         g = obj.grad(J)
         if (it & 3) == 3 and float(_inner(g, g).sqrt().max()) < 1e-9:
             break
@@ -278,8 +285,10 @@ def nsd_solve(prob, J0, maxiter=40, lr=None):
 # tests/test_rtr.py::test_rtr_body_matches_eager.
 # ---------------------------------------------------------------------------
 
-def _tcg_fixed(obj, J, grad, delta, maxit):
-    """_tcg without the host-side early-exit poll (capture-safe)."""
+def _tcg_fixed(obj, J, grad, delta, maxit, kappa=0.01, count=False):
+    """_tcg without the host-side early-exit poll (capture-safe). With
+    count=True returns (eta, nit): nit [n] counts the iterations a chunk
+    entered before its `done` was set."""
     n = J.shape[0]
     eta = torch.zeros_like(J)
     r = grad.clone()
@@ -287,8 +296,11 @@ def _tcg_fixed(obj, J, grad, delta, maxit):
     r0 = _inner(r, r)
     rnorm0 = r0.sqrt()
     done = torch.zeros(n, dtype=torch.bool, device=J.device)
-    tol = rnorm0 * torch.minimum(rnorm0, torch.full_like(rnorm0, 0.01))
+    tol = rnorm0 * torch.minimum(rnorm0, torch.full_like(rnorm0, kappa))
+    nit = torch.zeros_like(r0) if count else None
     for it in range(maxit):
+        if count:
+            nit = nit + (~done).to(nit.dtype)
         Hd = obj.hess_vec(J, d)
         dHd = _inner(d, Hd)
         alpha = _inner(r, r) / dHd.clamp_min(1e-30)
@@ -310,7 +322,19 @@ def _tcg_fixed(obj, J, grad, delta, maxit):
         beta = rn / r0.clamp_min(1e-30)
         d = -r + beta[:, None, None, None] * d
         r0 = rn
-    return eta
+    return (eta, nit) if count else eta
+
+
+def _kernel_step(obj, J, delta, maxit):
+    """(eta, model decrease) of one outer iteration from one ops.rtr_tcg:
+    the gradient at J, the truncated-CG step and hess_vec(J, eta) with the
+    three inner products of mdec, none of which torch then recomputes."""
+    _, eta, _, st = ops.rtr_tcg(obj.JtJ, obj.Jtr, J, obj.iw, delta, maxit)
+    return eta, -(st[:, 1] + 0.5 * st[:, 2])
+
+
+def _use_kernel(J):
+    return ops.rtr_kernel_on() and J.is_cuda and J.dtype == torch.complex64
 
 
 def _rtr_body(x, coh, bb, N, nchunk, chunk_rows, w, layout, J0, iw,
@@ -344,12 +368,17 @@ def _rtr_body(x, coh, bb, N, nchunk, chunk_rows, w, layout, J0, iw,
     g = obj.grad(J)
     delta = 0.1 * _inner(J, J).sqrt().clamp_min(1.0)
     delta_bar = delta * 8
+    kern = _use_kernel(J)
     for _ in range(maxiter):
-        eta = _tcg_fixed(obj, J, g, delta, tcg_maxit)
+        if kern:
+            eta, mdec = _kernel_step(obj, J, delta, tcg_maxit)
+        else:
+            eta = _tcg_fixed(obj, J, g, delta, tcg_maxit)
         Jn = J + eta
         cn = obj.cost(Jn)
-        Heta = obj.hess_vec(J, eta)
-        mdec = -(_inner(g, eta) + 0.5 * _inner(eta, Heta))
+        if not kern:
+            Heta = obj.hess_vec(J, eta)
+            mdec = -(_inner(g, eta) + 0.5 * _inner(eta, Heta))
         rho = (cost - cn) / mdec.clamp_min(1e-30)
         accept = (rho > 0.1) & (cn < cost)
         J = torch.where(accept[:, None, None, None], Jn, J)
@@ -359,7 +388,8 @@ def _rtr_body(x, coh, bb, N, nchunk, chunk_rows, w, layout, J0, iw,
                                         torch.minimum(delta * 2.0,
                                                       delta_bar), delta))
         obj.refresh(J)
-        g = obj.grad(J)
+        if not kern:
+            g = obj.grad(J)
     return J, cost, init_cost
 
 
@@ -382,7 +412,8 @@ def rtr_solve_graphed(prob, J0, maxiter=20, rsd_iters=2, tcg_maxit=12):
     dev = x.device
     B = x.shape[0]
     key = (B, nchunk, N, maxiter, rsd_iters, tcg_maxit,
-           ops_d.obj_token(prob.layout), prob.admm is not None)
+           ops_d.obj_token(prob.layout), prob.admm is not None,
+           _use_kernel(J0))
     ent = _rtr_graph_cache.get(key)
     if ent is None:
         ent = {'x': torch.empty_like(x), 'coh': torch.empty_like(coh),
