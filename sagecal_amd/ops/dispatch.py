@@ -48,6 +48,15 @@ def obj_token(obj):
     return tok
 
 
+def remember(cache, key, value, cap):
+    """cache[key] = value in a dict bounded for long multi-MS runs: once it
+    holds more than `cap` entries the oldest goes first. Returns value."""
+    if len(cache) > cap:
+        cache.pop(next(iter(cache)))
+    cache[key] = value
+    return value
+
+
 def have_ext():
     return _load_ext() is not None
 
@@ -246,9 +255,7 @@ _lbfgs_tab_memo = {}   # chunk tables and pair tables of lbfgs_cost_grad
 def _memo(key, build):
     hit = _lbfgs_tab_memo.get(key)
     if hit is None:
-        if len(_lbfgs_tab_memo) > 64:    # bound long multi-MS runs
-            _lbfgs_tab_memo.pop(next(iter(_lbfgs_tab_memo)))
-        hit = _lbfgs_tab_memo[key] = build()
+        hit = remember(_lbfgs_tab_memo, key, build(), 64)
     return hit
 
 

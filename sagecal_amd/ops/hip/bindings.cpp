@@ -22,53 +22,253 @@ static const float2* ccptr(const torch::Tensor& t) {
 static const double* dp(const torch::Tensor& t) { return t.data_ptr<double>(); }
 static const float* fp(const torch::Tensor& t) { return t.data_ptr<float>(); }
 static const int* ip(const torch::Tensor& t) { return t.data_ptr<int>(); }
+
+// The one tensor check: contiguous, of dtype ty, on the device dev and,
+// with n >= 0, of n elements. Dimensions and shapes stay with the caller.
+static bool on_dev(const torch::Tensor& t, const torch::Device& dev,
+                   torch::ScalarType ty, int64_t n = -1) {
+  return t.is_cuda() && t.device() == dev && t.scalar_type() == ty &&
+         t.is_contiguous() && (n < 0 || t.numel() == n);
+}
+
+// The kernels read 2x2 matrices as two 16-byte loads.
+static void check_aligned16(std::initializer_list<const torch::Tensor*> ts,
+                            const char* names) {
+  for (const torch::Tensor* t : ts)
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, names,
+                " must be 16-byte aligned");
+}
+
+// u, v, w: [R] float64 on one device, contiguous
 static RowsUVW rows_uvw(const torch::Tensor& u, const torch::Tensor& v,
                         const torch::Tensor& w) {
+  TORCH_CHECK(u.is_cuda() && u.dim() == 1, "u must be a device tensor [R]");
+  for (const torch::Tensor* t : {&u, &v, &w})
+    TORCH_CHECK(on_dev(*t, u.device(), torch::kDouble, u.size(0)),
+                "u, v, w must be contiguous [R] float64 on one device");
   RowsUVW rows = {};
   rows.u = dp(u); rows.v = dp(v); rows.w = dp(w);
   rows.R = (int)u.size(0);
   return rows;
 }
 
-// The optional station beam of both predict entry points: beam [T, K, N]
-// float32, pairs [Nbase, 2] int32 and ejones [T, K, NE, 2, 2] complex64,
-// checked against the rows of u. The kernels index all three by timeslot,
-// source and station with no bounds of their own, and read pairs on every
-// row with either buffer. Nsta_ej is the station count that ejones goes
-// with (beam brings its own).
+// The rows of the all-channels entry points: at least one, below 2^31.
+static RowsUVW rows_mf(const torch::Tensor& u, const torch::Tensor& v,
+                       const torch::Tensor& w) {
+  TORCH_CHECK(u.dim() == 1 && u.size(0) >= 1 &&
+              u.size(0) < (int64_t(1) << 31), "rows out of range");
+  return rows_uvw(u, v, w);
+}
+
+// A record is a Python dict from field name to tensor, described by one
+// table of rows (name, dtype, length kind, where the pointer goes).
+enum Len {
+  COUNT,      // n elements; the first row of a table sets n = size(0)
+  COUNT1,     // n + 1 elements
+  PREFIX,     // one-dimensional [M + 1]: its own length sets M
+  FREE        // any length; the record's function checks the shape
+};
+
+template <class Rec>
+struct Field {
+  const char* name;
+  torch::ScalarType ty;
+  Len len;
+  void (*set)(Rec&, const void*);
+};
+
+#define FIELD(Rec, key, member, ty, len)                    \
+  {#key, ty, len, [](Rec& r, const void* p) {               \
+     r.member = static_cast<decltype(r.member)>(p); }}
+
+// Fills rec from the dict d by the table `fields`: every field present, on
+// dev, of its dtype, contiguous and of its length, and no key besides them.
+// Returns n.
+template <class Rec, size_t NF>
+static int64_t read_record(const char* what, const py::dict& d,
+                           const Field<Rec> (&fields)[NF],
+                           const torch::Device& dev, Rec& rec) {
+  int64_t n = -1;
+  for (const Field<Rec>& f : fields) {
+    PyObject* item = PyDict_GetItemString(d.ptr(), f.name);   // borrowed
+    TORCH_CHECK(item != nullptr, what, " lacks the field ", f.name);
+    const torch::Tensor t = py::cast<torch::Tensor>(py::handle(item));
+    if (n < 0) {
+      TORCH_CHECK(t.dim() >= 1, what, ".", f.name, " must be [n]");
+      n = t.size(0);
+    }
+    const int64_t want = f.len == COUNT ? n : f.len == COUNT1 ? n + 1 : -1;
+    TORCH_CHECK(on_dev(t, dev, f.ty, want) &&
+                (f.len != PREFIX || (t.dim() == 1 && t.size(0) >= 1)),
+                what, ".", f.name, " must be contiguous ", f.ty,
+                f.len == PREFIX ? " [M + 1]" : "", want < 0 ? "" : " with ",
+                want < 0 ? "" : std::to_string(want).c_str(),
+                want < 0 ? "" : " elements", " on the device of u");
+    f.set(rec, t.data_ptr());
+  }
+  if (d.size() != NF)
+    for (auto kv : d) {
+      const std::string key = py::str(kv.first);
+      bool known = false;
+      for (const Field<Rec>& f : fields) known = known || key == f.name;
+      TORCH_CHECK(known, what, " has the unknown field ", key);
+    }
+  return n;
+}
+
+// hip_host.GPUPack.record: what k_predict_coh reads per source, K sources in M
+// clusters. The fluxes and r1 change per call (set_flux).
+static const Field<SourceArrays> SOURCE_FIELDS[] = {
+  FIELD(SourceArrays, ll, ll, torch::kDouble, COUNT),
+  FIELD(SourceArrays, mm, mm, torch::kDouble, COUNT),
+  FIELD(SourceArrays, nn1, nn1, torch::kDouble, COUNT),
+  FIELD(SourceArrays, eX, eX, torch::kFloat, COUNT),
+  FIELD(SourceArrays, eY, eY, torch::kFloat, COUNT),
+  FIELD(SourceArrays, eP, eP, torch::kFloat, COUNT),
+  FIELD(SourceArrays, cxi, cxi, torch::kFloat, COUNT),
+  FIELD(SourceArrays, sxi, sxi, torch::kFloat, COUNT),
+  FIELD(SourceArrays, cphi, cphi, torch::kFloat, COUNT),
+  FIELD(SourceArrays, sphi, sphi, torch::kFloat, COUNT),
+  FIELD(SourceArrays, stype, stype, torch::kInt, COUNT),
+  FIELD(SourceArrays, cluster_off, cluster_off, torch::kInt, PREFIX),
+};
+
+// The caller guarantees that cluster_off is non-decreasing from 0 to K.
+static SourceArrays source_arrays(const py::dict& src, const torch::Tensor& u,
+                                  int64_t& K) {
+  SourceArrays s = {};
+  K = read_record("src", src, SOURCE_FIELDS, u.device(), s);
+  s.M = (int)py::cast<torch::Tensor>(src["cluster_off"]).size(0) - 1;
+  return s;
+}
+
+// hip_host.ShapeletTable.record: the mode table of the shapelet kernels,
+// S entries. flux and r1 change per call.
+static const Field<ShapeletTabMF> SHAPELET_FIELDS[] = {
+  FIELD(ShapeletTabMF, src, t.src, torch::kInt, COUNT),
+  FIELD(ShapeletTabMF, cluster, t.cluster, torch::kInt, COUNT),
+  FIELD(ShapeletTabMF, n0, t.n0, torch::kInt, COUNT),
+  FIELD(ShapeletTabMF, beta, t.beta, torch::kFloat, COUNT),
+  FIELD(ShapeletTabMF, off, t.off, torch::kInt, COUNT1),
+  FIELD(ShapeletTabMF, coef, t.coef, torch::kFloat, FREE),
+  FIELD(ShapeletTabMF, cxi, t.cxi, torch::kFloat, COUNT),
+  FIELD(ShapeletTabMF, sxi, t.sxi, torch::kFloat, COUNT),
+  FIELD(ShapeletTabMF, cphi, t.cphi, torch::kFloat, COUNT),
+  FIELD(ShapeletTabMF, sphi, t.sphi, torch::kFloat, COUNT),
+  FIELD(ShapeletTabMF, psign, t.psign, torch::kFloat, COUNT),
+  FIELD(ShapeletTabMF, a, t.a, torch::kFloat, COUNT),
+  FIELD(ShapeletTabMF, b, t.b, torch::kFloat, COUNT),
+  FIELD(ShapeletTabMF, ceP, t.ceP, torch::kFloat, COUNT),
+  FIELD(ShapeletTabMF, seP, t.seP, torch::kFloat, COUNT),
+  FIELD(ShapeletTabMF, ll, t.ll, torch::kDouble, COUNT),
+  FIELD(ShapeletTabMF, mm, t.mm, torch::kDouble, COUNT),
+  FIELD(ShapeletTabMF, nn1, t.nn1, torch::kDouble, COUNT),
+  FIELD(ShapeletTabMF, rec, t.rec, torch::kFloat, FREE),
+  FIELD(ShapeletTabMF, entry_off, entry_off, torch::kInt, PREFIX),
+};
+
+// The single-channel kernel reads tab.t alone. The caller guarantees that
+// entry_off is non-decreasing from 0 to S and that src holds source indices
+// below K.
+static ShapeletTabMF shapelet_tab(const py::dict& tab, const torch::Tensor& u) {
+  ShapeletTabMF s = {};
+  s.t.S = (int)read_record("tab", tab, SHAPELET_FIELDS, u.device(), s);
+  const torch::Tensor rec = py::cast<torch::Tensor>(tab["rec"]);
+  TORCH_CHECK(rec.dim() == 2 && rec.size(0) == 2, "rec must be [2, max n0]");
+  s.t.nmax = (int)rec.size(1);
+  s.M = (int)py::cast<torch::Tensor>(tab["entry_off"]).size(0) - 1;
+  return s;
+}
+
+// The table of the all-channels shapelet kernels: at least one entry and
+// one cluster.
+static ShapeletTabMF shapelet_tab_mf(const py::dict& tab,
+                                     const torch::Tensor& u) {
+  const ShapeletTabMF s = shapelet_tab(tab, u);
+  TORCH_CHECK(s.t.S >= 1, "the shapelet table is empty");
+  TORCH_CHECK(s.M >= 1, "entry_off must be contiguous [M + 1] int32");
+  return s;
+}
+
+// The per-call arrays of the single-channel entry points: flux [4, n]
+// float32 (I, Q, U, V rows) and r1 [n] float32, n sources or table entries.
+static void check_flux_r1(const torch::Tensor& flux, const torch::Tensor& r1,
+                          int64_t n, const torch::Device& dev) {
+  TORCH_CHECK(on_dev(flux, dev, torch::kFloat, 4 * n) && flux.dim() == 2 &&
+              flux.size(0) == 4, "flux must be contiguous [4, ", n,
+              "] float32");
+  TORCH_CHECK(on_dev(r1, dev, torch::kFloat, n), "r1 must be contiguous [", n,
+              "] float32");
+}
+
+// The per-call arrays of the all-channels entry points: freqs [F] float64,
+// the flux stack [F, 4, n] float32 (I, Q, U, V rows per channel) and r1 [n].
+static Channels channels(const torch::Tensor& freqs, const torch::Tensor& flux,
+                         const torch::Tensor& r1, int64_t n, double fdelta2,
+                         double tdelta, const torch::Device& dev) {
+  TORCH_CHECK(on_dev(freqs, dev, torch::kDouble) && freqs.dim() == 1 &&
+              freqs.size(0) >= 1, "freqs must be contiguous [F] float64, "
+              "F >= 1");
+  const int64_t F = freqs.size(0);
+  TORCH_CHECK(on_dev(flux, dev, torch::kFloat) && flux.dim() == 3 &&
+              flux.size(0) == F && flux.size(1) == 4 && flux.size(2) == n,
+              "flux must be contiguous [F, 4, ", n, "] float32");
+  TORCH_CHECK(on_dev(r1, dev, torch::kFloat, n), "r1 must be contiguous [", n,
+              "] float32");
+  Channels ch = {};
+  ch.freqs = dp(freqs);
+  ch.F = (int)F;
+  ch.fdelta2 = fdelta2;
+  ch.tdelta = tdelta;
+  ch.flux_stride = 4 * n;
+  return ch;
+}
+
+// sI..sV are the rows of flux [4, K], or of channel 0 of [F, 4, K].
+static void set_flux(SourceArrays& s, const torch::Tensor& flux,
+                     const torch::Tensor& r1, int64_t K) {
+  s.sI = fp(flux); s.sQ = s.sI + K; s.sU = s.sI + 2 * K; s.sV = s.sI + 3 * K;
+  s.r1 = fp(r1);
+}
+
+// The pair table [Nbase, 2] int32 that a beam is indexed through.
+static const int* beam_pairs(const c10::optional<torch::Tensor>& pairs,
+                             int64_t Nbase, const torch::Device& dev) {
+  TORCH_CHECK(pairs.has_value() && Nbase > 0,
+              "beam and ejones need the station-pair table and Nbase");
+  TORCH_CHECK(on_dev(*pairs, dev, torch::kInt, 2 * Nbase),
+              "pairs must be contiguous [Nbase, 2] int32");
+  return ip(*pairs);
+}
+
+// The optional station beam of both single-channel entry points: beam
+// [T, K, N] float32, pairs [Nbase, 2] int32 and ejones [T, K, NE, 2, 2]
+// complex64, checked against the R rows. The kernels index all three by
+// timeslot, source and station with no bounds of their own, and read pairs
+// on every row with either buffer. Nsta_ej is the station count that ejones
+// goes with (beam brings its own).
 static BeamArgs beam_args(
     const c10::optional<torch::Tensor>& beam,
     const c10::optional<torch::Tensor>& pairs,
-    const c10::optional<torch::Tensor>& ejones, const torch::Tensor& u,
-    int64_t Nbase, int64_t Nsta_ej) {
+    const c10::optional<torch::Tensor>& ejones, int64_t R, int64_t Nbase,
+    int64_t Nsta_ej, const torch::Device& dev) {
   BeamArgs a = {};
   if (!beam.has_value() && !ejones.has_value()) return a;
-  const int64_t R = u.size(0);
-  TORCH_CHECK(pairs.has_value() && Nbase > 0,
-              "beam and ejones need the station-pair table and Nbase");
-  TORCH_CHECK(pairs->device() == u.device() &&
-              pairs->scalar_type() == torch::kInt && pairs->is_contiguous() &&
-              pairs->numel() == 2 * Nbase,
-              "pairs must be contiguous [Nbase, 2] int32");
-  a.pairs = pairs->data_ptr<int>();
+  a.pairs = beam_pairs(pairs, Nbase, dev);
   a.Nbase = (int)Nbase;
   if (beam.has_value()) {
-    TORCH_CHECK(beam->device() == u.device() &&
-                beam->scalar_type() == torch::kFloat &&
-                beam->is_contiguous() && beam->dim() == 3,
+    TORCH_CHECK(on_dev(*beam, dev, torch::kFloat) && beam->dim() == 3,
                 "beam must be contiguous [T, K, N] float32");
     TORCH_CHECK(R <= beam->size(0) * Nbase,
                 "beam has too few timeslots for the rows");
-    a.beam = beam->data_ptr<float>();
+    a.beam = fp(*beam);
     a.Ktot = (int)beam->size(1);
     a.Nsta = (int)beam->size(2);
   }
   if (ejones.has_value()) {
     const torch::Tensor& e = *ejones;
-    TORCH_CHECK(e.is_cuda() && e.device() == u.device() &&
-                e.scalar_type() == torch::kComplexFloat &&
-                e.is_contiguous() && e.dim() == 5 && e.size(3) == 2 &&
-                e.size(4) == 2,
+    TORCH_CHECK(on_dev(e, dev, torch::kComplexFloat) && e.dim() == 5 &&
+                e.size(3) == 2 && e.size(4) == 2,
                 "ejones must be contiguous [T, K, NE, 2, 2] complex64");
     TORCH_CHECK(e.size(0) * Nbase == R, "ejones timeslots * Nbase != rows");
     TORCH_CHECK(Nsta_ej > 0, "ejones needs the station count Nsta");
@@ -86,26 +286,21 @@ static BeamArgs beam_args(
   return a;
 }
 
+// Coherencies [M, R, 4] complex64 of the pack record `src` at one channel
+// (k_predict_coh, with ejones k_predict_coh_ej): flux [4, K], r1 [K].
 torch::Tensor predict_coh(
-    torch::Tensor u, torch::Tensor v, torch::Tensor w,
-    torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
-    torch::Tensor sI, torch::Tensor sQ, torch::Tensor sU, torch::Tensor sV,
-    torch::Tensor eX, torch::Tensor eY, torch::Tensor eP,
-    torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
-    torch::Tensor sphi, torch::Tensor r1, torch::Tensor stype,
-    torch::Tensor cluster_off, double freq, double fdelta2, double tdelta,
-    c10::optional<torch::Tensor> beam, c10::optional<torch::Tensor> pairs,
-    int64_t Nbase, c10::optional<torch::Tensor> ejones, int64_t Nsta_ej) {
-  const BeamArgs bm = beam_args(beam, pairs, ejones, u, Nbase, Nsta_ej);
+    torch::Tensor u, torch::Tensor v, torch::Tensor w, py::dict src_rec,
+    torch::Tensor flux, torch::Tensor r1, double freq, double fdelta2,
+    double tdelta, c10::optional<torch::Tensor> beam,
+    c10::optional<torch::Tensor> pairs, int64_t Nbase,
+    c10::optional<torch::Tensor> ejones, int64_t Nsta_ej) {
   const RowsUVW rows = rows_uvw(u, v, w);
-  SourceArrays src = {};
-  src.ll = dp(ll); src.mm = dp(mm); src.nn1 = dp(nn1);
-  src.sI = fp(sI); src.sQ = fp(sQ); src.sU = fp(sU); src.sV = fp(sV);
-  src.eX = fp(eX); src.eY = fp(eY); src.eP = fp(eP);
-  src.cxi = fp(cxi); src.sxi = fp(sxi); src.cphi = fp(cphi);
-  src.sphi = fp(sphi); src.r1 = fp(r1);
-  src.stype = ip(stype); src.cluster_off = ip(cluster_off);
-  src.M = (int)cluster_off.size(0) - 1;
+  int64_t K;
+  SourceArrays src = source_arrays(src_rec, u, K);
+  check_flux_r1(flux, r1, K, u.device());
+  set_flux(src, flux, r1, K);
+  const BeamArgs bm = beam_args(beam, pairs, ejones, rows.R, Nbase, Nsta_ej,
+                                u.device());
   auto out = torch::empty({src.M, rows.R, 4},
       torch::dtype(torch::kComplexFloat).device(u.device()));
   CHECK_HIP(launch_predict_coh(rows, src, {freq, fdelta2, tdelta}, bm,
@@ -113,225 +308,64 @@ torch::Tensor predict_coh(
   return out;
 }
 
-// The mode table of hip_host.ShapeletTable, checked against the device of
-// u and its S = src.size(0) entries; flux and r1 are left to the caller.
-static ShapeletTab shapelet_tab(
-    const torch::Tensor& u, const torch::Tensor& src,
-    const torch::Tensor& cluster, const torch::Tensor& n0,
-    const torch::Tensor& beta, const torch::Tensor& off,
-    const torch::Tensor& coef, const torch::Tensor& cxi,
-    const torch::Tensor& sxi, const torch::Tensor& cphi,
-    const torch::Tensor& sphi, const torch::Tensor& psign,
-    const torch::Tensor& a, const torch::Tensor& b, const torch::Tensor& ceP,
-    const torch::Tensor& seP, const torch::Tensor& ll,
-    const torch::Tensor& mm, const torch::Tensor& nn1,
-    const torch::Tensor& rec) {
-  const int64_t S = src.size(0);
-  auto chk = [&](const torch::Tensor& t, torch::ScalarType ty, int64_t n,
-                 const char* name) {
-    TORCH_CHECK(t.device() == u.device(), name, " is on another device");
-    TORCH_CHECK(t.scalar_type() == ty, name, " has the wrong dtype");
-    TORCH_CHECK(t.is_contiguous() && t.numel() == n, name,
-                " must be contiguous with ", n, " elements");
-  };
-  chk(src, torch::kInt, S, "src");
-  chk(cluster, torch::kInt, S, "cluster");
-  chk(n0, torch::kInt, S, "n0");
-  chk(beta, torch::kFloat, S, "beta");
-  chk(off, torch::kInt, S + 1, "off");
-  TORCH_CHECK(coef.scalar_type() == torch::kFloat && coef.is_contiguous() &&
-              coef.device() == u.device(), "coef must be contiguous float32");
-  chk(cxi, torch::kFloat, S, "cxi");
-  chk(sxi, torch::kFloat, S, "sxi");
-  chk(cphi, torch::kFloat, S, "cphi");
-  chk(sphi, torch::kFloat, S, "sphi");
-  chk(psign, torch::kFloat, S, "psign");
-  chk(a, torch::kFloat, S, "a");
-  chk(b, torch::kFloat, S, "b");
-  chk(ceP, torch::kFloat, S, "ceP");
-  chk(seP, torch::kFloat, S, "seP");
-  chk(ll, torch::kDouble, S, "ll");
-  chk(mm, torch::kDouble, S, "mm");
-  chk(nn1, torch::kDouble, S, "nn1");
-  TORCH_CHECK(rec.dim() == 2 && rec.size(0) == 2, "rec must be [2, max n0]");
-  chk(rec, torch::kFloat, rec.numel(), "rec");
-  ShapeletTab tab = {};
-  tab.src = ip(src); tab.cluster = ip(cluster); tab.n0 = ip(n0);
-  tab.beta = fp(beta); tab.off = ip(off); tab.coef = fp(coef);
-  tab.cxi = fp(cxi); tab.sxi = fp(sxi); tab.cphi = fp(cphi);
-  tab.sphi = fp(sphi); tab.psign = fp(psign); tab.a = fp(a); tab.b = fp(b);
-  tab.ceP = fp(ceP); tab.seP = fp(seP);
-  tab.ll = dp(ll); tab.mm = dp(mm); tab.nn1 = dp(nn1);
-  tab.rec = fp(rec); tab.S = (int)S; tab.nmax = (int)rec.size(1);
-  return tab;
-}
-
-// u, v, w: [R] float64 on one device, contiguous
-static void check_uvw(const torch::Tensor& u, const torch::Tensor& v,
-                      const torch::Tensor& w) {
-  TORCH_CHECK(u.is_cuda() && u.dim() == 1, "u must be a device tensor [R]");
-  for (const torch::Tensor* t : {&u, &v, &w})
-    TORCH_CHECK(t->device() == u.device() &&
-                t->scalar_type() == torch::kDouble && t->is_contiguous() &&
-                t->numel() == u.size(0),
-                "u, v, w must be contiguous [R] float64 on one device");
-}
-
-// Adds the shapelet sources of a ShapeletTable (hip_host.py) into `out`
-// [M, R, 4] complex64, in place, on the current stream.
+// Adds the shapelet sources of the table record `tab` into `out` [M, R, 4]
+// complex64, in place, on the current stream: flux [4, S], r1 [S].
 void shapelet_coh_add(
     torch::Tensor out, torch::Tensor u, torch::Tensor v, torch::Tensor w,
-    torch::Tensor src, torch::Tensor cluster, torch::Tensor n0,
-    torch::Tensor beta, torch::Tensor off, torch::Tensor coef,
-    torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
-    torch::Tensor sphi, torch::Tensor psign, torch::Tensor a,
-    torch::Tensor b, torch::Tensor ceP, torch::Tensor seP,
-    torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
-    torch::Tensor rec, torch::Tensor flux, torch::Tensor r1,
-    double freq, double fdelta2, double tdelta,
-    c10::optional<torch::Tensor> beam, c10::optional<torch::Tensor> pairs,
-    int64_t Nbase, c10::optional<torch::Tensor> ejones, int64_t Nsta_ej) {
-  const int64_t R = u.size(0);
-  const int64_t S = src.size(0);
-  check_uvw(u, v, w);
-  TORCH_CHECK(out.device() == u.device() &&
-              out.scalar_type() == torch::kComplexFloat &&
-              out.is_contiguous() && out.dim() == 3 && out.size(1) == R &&
-              out.size(2) == 4, "out must be contiguous [M, R, 4] complex64");
-  ShapeletTab tab = shapelet_tab(u, src, cluster, n0, beta, off, coef, cxi,
-                                 sxi, cphi, sphi, psign, a, b, ceP, seP, ll,
-                                 mm, nn1, rec);
-  auto flt = [&](const torch::Tensor& t, int64_t n) {
-    return t.device() == u.device() && t.scalar_type() == torch::kFloat &&
-           t.is_contiguous() && t.numel() == n;
-  };
-  TORCH_CHECK(flt(flux, 4 * S), "flux must be contiguous [4, S] float32");
-  TORCH_CHECK(flt(r1, S), "r1 must be contiguous [S] float32");
-  const BeamArgs bm = beam_args(beam, pairs, ejones, u, Nbase, Nsta_ej);
+    py::dict tab_rec, torch::Tensor flux, torch::Tensor r1, double freq,
+    double fdelta2, double tdelta, c10::optional<torch::Tensor> beam,
+    c10::optional<torch::Tensor> pairs, int64_t Nbase,
+    c10::optional<torch::Tensor> ejones, int64_t Nsta_ej) {
+  const RowsUVW rows = rows_uvw(u, v, w);
+  TORCH_CHECK(on_dev(out, u.device(), torch::kComplexFloat) &&
+              out.dim() == 3 && out.size(1) == rows.R && out.size(2) == 4,
+              "out must be contiguous [M, R, 4] complex64");
+  ShapeletTab tab = shapelet_tab(tab_rec, u).t;
+  check_flux_r1(flux, r1, tab.S, u.device());
   tab.flux = fp(flux); tab.r1 = fp(r1);
-  CHECK_HIP(launch_shapelet_coh(rows_uvw(u, v, w), tab,
-                                {freq, fdelta2, tdelta}, bm, cptr(out),
-                                cur_stream()));
+  const BeamArgs bm = beam_args(beam, pairs, ejones, rows.R, Nbase, Nsta_ej,
+                                u.device());
+  CHECK_HIP(launch_shapelet_coh(rows, tab, {freq, fdelta2, tdelta}, bm,
+                                cptr(out), cur_stream()));
 }
 
-// The arguments the two all-channels entry points share, checked: every
-// per-source tensor has K entries, flux is [F, 4, K] float32 (I, Q, U, V
-// rows per channel), freqs [F] float64, all on u's device and contiguous.
-struct MfArgs {
-  RowsUVW rows;
-  SourceArrays src;
-  Channels ch;
-};
-
-static MfArgs mf_args(
-    const torch::Tensor& u, const torch::Tensor& v, const torch::Tensor& w,
-    const torch::Tensor& ll, const torch::Tensor& mm,
-    const torch::Tensor& nn1, const torch::Tensor& flux,
-    const torch::Tensor& eX, const torch::Tensor& eY,
-    const torch::Tensor& eP, const torch::Tensor& cxi,
-    const torch::Tensor& sxi, const torch::Tensor& cphi,
-    const torch::Tensor& sphi, const torch::Tensor& r1,
-    const torch::Tensor& stype, const torch::Tensor& cluster_off,
-    const torch::Tensor& freqs, double fdelta2, double tdelta) {
-  TORCH_CHECK(u.is_cuda() && u.dim() == 1, "u must be a device tensor [R]");
-  const int64_t R = u.size(0), K = ll.size(0);
-  auto chk = [&](const torch::Tensor& t, torch::ScalarType ty, int64_t n,
-                 const char* name) {
-    TORCH_CHECK(t.device() == u.device(), name, " is on another device");
-    TORCH_CHECK(t.scalar_type() == ty, name, " has the wrong dtype");
-    TORCH_CHECK(t.is_contiguous() && t.numel() == n, name,
-                " must be contiguous with ", n, " elements");
-  };
-  chk(u, torch::kDouble, R, "u");
-  chk(v, torch::kDouble, R, "v");
-  chk(w, torch::kDouble, R, "w");
-  chk(ll, torch::kDouble, K, "ll");
-  chk(mm, torch::kDouble, K, "mm");
-  chk(nn1, torch::kDouble, K, "nn1");
-  chk(eX, torch::kFloat, K, "eX");
-  chk(eY, torch::kFloat, K, "eY");
-  chk(eP, torch::kFloat, K, "eP");
-  chk(cxi, torch::kFloat, K, "cxi");
-  chk(sxi, torch::kFloat, K, "sxi");
-  chk(cphi, torch::kFloat, K, "cphi");
-  chk(sphi, torch::kFloat, K, "sphi");
-  chk(r1, torch::kFloat, K, "r1");
-  chk(stype, torch::kInt, K, "stype");
-  TORCH_CHECK(freqs.dim() == 1 && freqs.size(0) >= 1, "freqs must be [F], "
-              "F >= 1");
-  const int64_t F = freqs.size(0);
-  chk(freqs, torch::kDouble, F, "freqs");
-  TORCH_CHECK(flux.dim() == 3 && flux.size(0) == F && flux.size(1) == 4,
-              "flux must be [F, 4, K]");
-  chk(flux, torch::kFloat, F * 4 * K, "flux");
-  TORCH_CHECK(cluster_off.dim() == 1 && cluster_off.size(0) >= 1,
-              "cluster_off must be [M + 1]");
-  chk(cluster_off, torch::kInt, cluster_off.size(0), "cluster_off");
-  TORCH_CHECK(R >= 1 && R < (int64_t(1) << 31), "rows out of range");
-  MfArgs a = {};
-  a.rows = rows_uvw(u, v, w);
-  a.src.ll = dp(ll); a.src.mm = dp(mm); a.src.nn1 = dp(nn1);
-  a.src.sI = fp(flux); a.src.sQ = fp(flux) + K;
-  a.src.sU = fp(flux) + 2 * K; a.src.sV = fp(flux) + 3 * K;
-  a.src.eX = fp(eX); a.src.eY = fp(eY); a.src.eP = fp(eP);
-  a.src.cxi = fp(cxi); a.src.sxi = fp(sxi); a.src.cphi = fp(cphi);
-  a.src.sphi = fp(sphi); a.src.r1 = fp(r1);
-  a.src.stype = ip(stype); a.src.cluster_off = ip(cluster_off);
-  a.src.M = (int)cluster_off.size(0) - 1;
-  a.ch.freqs = dp(freqs);
-  a.ch.F = (int)F;
-  a.ch.fdelta2 = fdelta2;
-  a.ch.tdelta = tdelta;
-  a.ch.flux_stride = 4 * K;
-  return a;
-}
-
-// The optional station beam of the two all-channels entry points: beam
+// The optional station beam of the all-channels entry points: beam
 // [F, T, Ke, N] float32, ejones [F, T, Ke, NE, 2, 2] complex64 and pairs
-// [Nbase, 2] int32, checked against the F channels, R rows and K sources of
-// `a`. The kernels index the buffers by channel, timeslot, source and
-// station with no bounds of their own; the caller guarantees pair entries
-// below the station count (negative ones only where the kernel keeps x).
-// Nsta_ej is the station count that ejones goes with (beam brings its own).
+// [Nbase, 2] int32, checked against the F channels, R rows and K sources.
+// The kernels index the buffers by channel, timeslot, source and station
+// with no bounds of their own; the caller guarantees pair entries below the
+// station count (negative ones only where the kernel keeps x). Nsta_ej is
+// the station count that ejones goes with (beam brings its own).
 static BeamChannels beam_channels(
     const c10::optional<torch::Tensor>& beam,
     const c10::optional<torch::Tensor>& ejones,
     const c10::optional<torch::Tensor>& pairs, int64_t Nbase,
-    int64_t Nsta_ej, const MfArgs& a, int64_t K, const torch::Tensor& u) {
+    int64_t Nsta_ej, int64_t R, int64_t F, int64_t K,
+    const torch::Device& dev) {
   BeamChannels b = {};
   if (!beam.has_value() && !ejones.has_value()) return b;
-  const int64_t R = a.rows.R, F = a.ch.F;
-  TORCH_CHECK(pairs.has_value() && Nbase > 0,
-              "beam and ejones need the station-pair table and Nbase");
-  TORCH_CHECK(pairs->device() == u.device() &&
-              pairs->scalar_type() == torch::kInt && pairs->is_contiguous() &&
-              pairs->numel() == 2 * Nbase,
-              "pairs must be contiguous [Nbase, 2] int32");
+  b.pairs = beam_pairs(pairs, Nbase, dev);
   TORCH_CHECK(R % Nbase == 0, "rows must be T * Nbase");
   const int64_t T = R / Nbase;
-  b.pairs = pairs->data_ptr<int>();
   b.Nbase = (int)Nbase;
   b.T = (int)T;
   auto fits = [](int64_t n) { return n >= 1 && n < (int64_t(1) << 31); };
   if (beam.has_value()) {
     const torch::Tensor& g = *beam;
-    TORCH_CHECK(g.device() == u.device() &&
-                g.scalar_type() == torch::kFloat && g.is_contiguous() &&
-                g.dim() == 4, "beam must be contiguous [F, T, K, N] float32");
+    TORCH_CHECK(on_dev(g, dev, torch::kFloat) && g.dim() == 4,
+                "beam must be contiguous [F, T, K, N] float32");
     TORCH_CHECK(g.size(0) == F && g.size(1) == T,
                 "beam must hold the F channels and T timeslots of the rows");
     TORCH_CHECK(g.size(2) >= K && fits(g.size(2)) && fits(g.size(3)),
                 "beam covers fewer sources than the pack");
-    b.beam = g.data_ptr<float>();
+    b.beam = fp(g);
     b.Ktot = (int)g.size(2);
     b.Nsta = (int)g.size(3);
   }
   if (ejones.has_value()) {
     const torch::Tensor& e = *ejones;
-    TORCH_CHECK(e.device() == u.device() &&
-                e.scalar_type() == torch::kComplexFloat &&
-                e.is_contiguous() && e.dim() == 6 && e.size(4) == 2 &&
-                e.size(5) == 2,
+    TORCH_CHECK(on_dev(e, dev, torch::kComplexFloat) && e.dim() == 6 &&
+                e.size(4) == 2 && e.size(5) == 2,
                 "ejones must be contiguous [F, T, K, NE, 2, 2] complex64");
     TORCH_CHECK(e.size(0) == F && e.size(1) == T,
                 "ejones must hold the F channels and T timeslots of the rows");
@@ -351,178 +385,135 @@ static BeamChannels beam_channels(
   return b;
 }
 
-// Coherencies of all F channels in one launch (k_predict_coh_mf):
-// [F, M, R, 4] complex64, or with mean their channel mean [M, R, 4]
-// (k_predict_coh_mean); with beam and/or ejones the _bm / _ej kernels. The
-// caller guarantees that cluster_off is non-decreasing from 0 to K.
-torch::Tensor predict_coh_channels(
-    torch::Tensor u, torch::Tensor v, torch::Tensor w,
-    torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
-    torch::Tensor flux, torch::Tensor eX, torch::Tensor eY, torch::Tensor eP,
-    torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
-    torch::Tensor sphi, torch::Tensor r1, torch::Tensor stype,
-    torch::Tensor cluster_off, torch::Tensor freqs, double fdelta2,
-    double tdelta, bool mean, c10::optional<torch::Tensor> beam,
-    c10::optional<torch::Tensor> ejones, c10::optional<torch::Tensor> pairs,
-    int64_t Nbase, int64_t Nsta_ej) {
-  const MfArgs a = mf_args(u, v, w, ll, mm, nn1, flux, eX, eY, eP, cxi, sxi,
-                           cphi, sphi, r1, stype, cluster_off, freqs,
-                           fdelta2, tdelta);
-  const BeamChannels bm = beam_channels(beam, ejones, pairs, Nbase, Nsta_ej,
-                                        a, ll.size(0), u);
-  auto copts = torch::dtype(torch::kComplexFloat).device(u.device());
-  auto out = mean ? torch::empty({a.src.M, a.rows.R, 4}, copts)
-                  : torch::empty({a.ch.F, a.src.M, a.rows.R, 4}, copts);
-  CHECK_HIP(launch_predict_coh_mf(a.rows, a.src, a.ch, bm, mean ? 1 : 0,
-                                  cptr(out), cur_stream()));
-  return out;
-}
-
-// x - sum over clusters with skip == 0 of J_p C J_q^H for all F channels in
-// one launch (k_residual_mf): x [F, R, 4] complex64, J [Mt, N, 4]
-// complex64, chunk_tab [M, T] int32 global chunk ids, pairs [Nbase, 2]
-// int32, R == T * Nbase, skip [M] int32 or none. Returns [F, R, 4]. The
-// caller guarantees chunk ids below Mt and pair entries below N. With beam
-// [F, T, Ke, Nsta] and/or ejones [F, T, Ke, NE, 2, 2] the coherencies carry
-// the station beam (k_residual_mf_bm / _ej), indexed through the same pairs.
-torch::Tensor residuals_multifreq(
-    torch::Tensor x, torch::Tensor u, torch::Tensor v, torch::Tensor w,
-    torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
-    torch::Tensor flux, torch::Tensor eX, torch::Tensor eY, torch::Tensor eP,
-    torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
-    torch::Tensor sphi, torch::Tensor r1, torch::Tensor stype,
-    torch::Tensor cluster_off, torch::Tensor freqs, double fdelta2,
-    double tdelta, torch::Tensor J, torch::Tensor chunk_tab,
-    torch::Tensor pairs, c10::optional<torch::Tensor> skip,
-    c10::optional<torch::Tensor> beam, c10::optional<torch::Tensor> ejones,
-    int64_t Nsta_ej) {
-  const MfArgs a = mf_args(u, v, w, ll, mm, nn1, flux, eX, eY, eP, cxi, sxi,
-                           cphi, sphi, r1, stype, cluster_off, freqs,
-                           fdelta2, tdelta);
-  const int64_t R = a.rows.R, F = a.ch.F, M = a.src.M;
-  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType ty) {
-    return t.device() == u.device() && t.scalar_type() == ty &&
-           t.is_contiguous();
-  };
-  TORCH_CHECK(on_dev(x, torch::kComplexFloat) && x.dim() == 3 &&
-              x.size(0) == F && x.size(1) == R && x.size(2) == 4,
-              "x must be contiguous [F, R, 4] complex64");
-  TORCH_CHECK(on_dev(J, torch::kComplexFloat) && J.dim() == 3 &&
+// J [Mt, N, 4] complex64 packed solutions, chunk_tab [M, T] and pairs
+// [Nbase, 2] int32 on dev, for R == T * Nbase rows. The caller guarantees
+// chunk ids below Mt and pair entries below N.
+static void check_solution_tables(
+    const torch::Tensor& J, const torch::Tensor& chunk_tab,
+    const torch::Tensor& pairs, int64_t M, int64_t R,
+    const torch::Device& dev) {
+  TORCH_CHECK(on_dev(J, dev, torch::kComplexFloat) && J.dim() == 3 &&
               J.size(0) >= 1 && J.size(1) >= 1 && J.size(2) == 4,
               "J must be contiguous [Mt, N, 4] complex64");
-  TORCH_CHECK(on_dev(chunk_tab, torch::kInt) && chunk_tab.dim() == 2 &&
+  TORCH_CHECK(on_dev(chunk_tab, dev, torch::kInt) && chunk_tab.dim() == 2 &&
               chunk_tab.size(0) == M && chunk_tab.size(1) >= 1,
               "chunk_tab must be contiguous [M, T] int32");
-  TORCH_CHECK(on_dev(pairs, torch::kInt) && pairs.dim() == 2 &&
+  TORCH_CHECK(on_dev(pairs, dev, torch::kInt) && pairs.dim() == 2 &&
               pairs.size(0) >= 1 && pairs.size(1) == 2,
               "pairs must be contiguous [Nbase, 2] int32");
-  TORCH_CHECK(chunk_tab.size(1) * pairs.size(0) == R,
-              "rows must be T * Nbase");
+  TORCH_CHECK(chunk_tab.size(1) * pairs.size(0) == R &&
+              R < (int64_t(1) << 31), "rows must be T * Nbase, below 2^31");
+}
+
+// What the two residual entry points take besides the predict arguments:
+// the tables of check_solution_tables and skip [M] int32 or none. x is left
+// to the caller.
+static ResidualArgs residual_args(
+    const torch::Tensor& J, const torch::Tensor& chunk_tab,
+    const torch::Tensor& pairs, const c10::optional<torch::Tensor>& skip,
+    int64_t M, int64_t R, const torch::Device& dev) {
+  check_solution_tables(J, chunk_tab, pairs, M, R, dev);
   ResidualArgs res = {};
-  res.x = ccptr(x);
   res.J = ccptr(J);
   res.chunk_tab = ip(chunk_tab);
   res.pairs = ip(pairs);
   if (skip.has_value()) {
-    TORCH_CHECK(on_dev(*skip, torch::kInt) && skip->numel() == M,
+    TORCH_CHECK(on_dev(*skip, dev, torch::kInt, M),
                 "skip must be contiguous [M] int32");
     res.skip = ip(*skip);
   }
   res.Nbase = (int)pairs.size(0);
   res.T = (int)chunk_tab.size(1);
   res.N = (int)J.size(1);
-  const BeamChannels bm = beam_channels(beam, ejones, pairs, pairs.size(0),
-                                        Nsta_ej, a, ll.size(0), u);
-  auto out = torch::empty({F, R, 4},
-      torch::dtype(torch::kComplexFloat).device(u.device()));
-  CHECK_HIP(launch_residual_mf(a.rows, a.src, a.ch, bm, res, cptr(out),
-                               cur_stream()));
+  return res;
+}
+
+// Coherencies of all F channels in one launch (k_predict_coh_mf):
+// [F, M, R, 4] complex64, or with mean their channel mean [M, R, 4]
+// (k_predict_coh_mean); with beam and/or ejones the _bm / _ej kernels. src is
+// the pack record, flux [F, 4, K], r1 [K].
+torch::Tensor predict_coh_channels(
+    torch::Tensor u, torch::Tensor v, torch::Tensor w, py::dict src_rec,
+    torch::Tensor flux, torch::Tensor r1, torch::Tensor freqs, double fdelta2,
+    double tdelta, bool mean, c10::optional<torch::Tensor> beam,
+    c10::optional<torch::Tensor> ejones, c10::optional<torch::Tensor> pairs,
+    int64_t Nbase, int64_t Nsta_ej) {
+  const torch::Device dev = u.device();
+  const RowsUVW rows = rows_mf(u, v, w);
+  int64_t K;
+  SourceArrays src = source_arrays(src_rec, u, K);
+  const Channels ch = channels(freqs, flux, r1, K, fdelta2, tdelta, dev);
+  set_flux(src, flux, r1, K);
+  const BeamChannels bm = beam_channels(beam, ejones, pairs, Nbase, Nsta_ej,
+                                        rows.R, ch.F, K, dev);
+  auto copts = torch::dtype(torch::kComplexFloat).device(dev);
+  auto out = mean ? torch::empty({src.M, rows.R, 4}, copts)
+                  : torch::empty({ch.F, src.M, rows.R, 4}, copts);
+  CHECK_HIP(launch_predict_coh_mf(rows, src, ch, bm, mean ? 1 : 0, cptr(out),
+                                  cur_stream()));
   return out;
 }
 
-// What the two all-channels shapelet entry points share, checked: the rows,
-// the table with its [M + 1] entry prefix, the flux stack [F, 4, S] and r1
-// [S], and the channels. The caller guarantees that entry_off is
-// non-decreasing from 0 to S and that src holds source indices below K.
-struct ShapeletMfArgs {
-  MfArgs a;                 // rows and ch; src unused
-  ShapeletTabMF tab;
-};
-
-static ShapeletMfArgs shapelet_mf_args(
-    const torch::Tensor& u, const torch::Tensor& v, const torch::Tensor& w,
-    ShapeletTab t, const torch::Tensor& entry_off, const torch::Tensor& flux,
-    const torch::Tensor& r1, const torch::Tensor& freqs, double fdelta2,
-    double tdelta) {
-  check_uvw(u, v, w);
-  const int64_t R = u.size(0), S = t.S;
-  TORCH_CHECK(R >= 1 && R < (int64_t(1) << 31), "rows out of range");
-  TORCH_CHECK(S >= 1, "the shapelet table is empty");
-  auto on_dev = [&](const torch::Tensor& x, torch::ScalarType ty) {
-    return x.device() == u.device() && x.scalar_type() == ty &&
-           x.is_contiguous();
-  };
-  TORCH_CHECK(on_dev(freqs, torch::kDouble) && freqs.dim() == 1 &&
-              freqs.size(0) >= 1, "freqs must be contiguous [F] float64, "
-              "F >= 1");
-  const int64_t F = freqs.size(0);
-  TORCH_CHECK(on_dev(flux, torch::kFloat) && flux.dim() == 3 &&
-              flux.size(0) == F && flux.size(1) == 4 && flux.size(2) == S,
-              "flux must be contiguous [F, 4, S] float32");
-  TORCH_CHECK(on_dev(r1, torch::kFloat) && r1.numel() == S,
-              "r1 must be contiguous [S] float32");
-  TORCH_CHECK(on_dev(entry_off, torch::kInt) && entry_off.dim() == 1 &&
-              entry_off.size(0) >= 2,
-              "entry_off must be contiguous [M + 1] int32");
-  ShapeletMfArgs s = {};
-  s.a.rows = rows_uvw(u, v, w);
-  s.a.ch.freqs = dp(freqs);
-  s.a.ch.F = (int)F;
-  s.a.ch.fdelta2 = fdelta2;
-  s.a.ch.tdelta = tdelta;
-  s.a.ch.flux_stride = 4 * S;
-  s.tab.t = t;
-  s.tab.t.flux = fp(flux);
-  s.tab.t.r1 = fp(r1);
-  s.tab.entry_off = ip(entry_off);
-  s.tab.M = (int)entry_off.size(0) - 1;
-  return s;
+// x - sum over clusters with skip == 0 of J_p C J_q^H for all F channels in
+// one launch (k_residual_mf): x [F, R, 4] complex64, the tables of
+// residual_args. Returns [F, R, 4]. With beam [F, T, Ke, Nsta] and/or ejones
+// [F, T, Ke, NE, 2, 2] the coherencies carry the station beam
+// (k_residual_mf_bm / _ej), indexed through the same pairs.
+torch::Tensor residuals_multifreq(
+    torch::Tensor x, torch::Tensor u, torch::Tensor v, torch::Tensor w,
+    py::dict src_rec, torch::Tensor flux, torch::Tensor r1,
+    torch::Tensor freqs, double fdelta2, double tdelta, torch::Tensor J,
+    torch::Tensor chunk_tab, torch::Tensor pairs,
+    c10::optional<torch::Tensor> skip, c10::optional<torch::Tensor> beam,
+    c10::optional<torch::Tensor> ejones, int64_t Nsta_ej) {
+  const torch::Device dev = u.device();
+  const RowsUVW rows = rows_mf(u, v, w);
+  int64_t K;
+  SourceArrays src = source_arrays(src_rec, u, K);
+  const Channels ch = channels(freqs, flux, r1, K, fdelta2, tdelta, dev);
+  set_flux(src, flux, r1, K);
+  const int64_t R = rows.R, F = ch.F;
+  TORCH_CHECK(on_dev(x, dev, torch::kComplexFloat) && x.dim() == 3 &&
+              x.size(0) == F && x.size(1) == R && x.size(2) == 4,
+              "x must be contiguous [F, R, 4] complex64");
+  ResidualArgs res = residual_args(J, chunk_tab, pairs, skip, src.M, R, dev);
+  res.x = ccptr(x);
+  const BeamChannels bm = beam_channels(beam, ejones, pairs, pairs.size(0),
+                                        Nsta_ej, R, F, K, dev);
+  auto out = torch::empty({F, R, 4},
+      torch::dtype(torch::kComplexFloat).device(dev));
+  CHECK_HIP(launch_residual_mf(rows, src, ch, bm, res, cptr(out),
+                               cur_stream()));
+  return out;
 }
 
 // Adds the shapelet sources of all F channels into `out`, what
 // predict_coh_channels returned for the same rows, channels, mean and beam
 // (k_shapelet_coh_mf / _mean, with beam and/or ejones _bm / _ej): [F, M, R,
-// 4] complex64, or with mean [M, R, 4]. In place, on the current stream. K
-// is the source count of the pack, which beam and ejones must cover.
+// 4] complex64, or with mean [M, R, 4]. In place, on the current stream. tab
+// is the table record, flux [F, 4, S], r1 [S]; K is the source count of the
+// pack, which beam and ejones must cover.
 void shapelet_coh_channels_add(
     torch::Tensor out, torch::Tensor u, torch::Tensor v, torch::Tensor w,
-    torch::Tensor src, torch::Tensor cluster, torch::Tensor n0,
-    torch::Tensor beta, torch::Tensor off, torch::Tensor coef,
-    torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
-    torch::Tensor sphi, torch::Tensor psign, torch::Tensor a,
-    torch::Tensor b, torch::Tensor ceP, torch::Tensor seP,
-    torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
-    torch::Tensor rec, torch::Tensor entry_off, torch::Tensor flux,
-    torch::Tensor r1, torch::Tensor freqs, double fdelta2, double tdelta,
-    bool mean, int64_t K, c10::optional<torch::Tensor> beam,
-    c10::optional<torch::Tensor> ejones, c10::optional<torch::Tensor> pairs,
-    int64_t Nbase, int64_t Nsta_ej) {
-  const ShapeletMfArgs s = shapelet_mf_args(
-      u, v, w, shapelet_tab(u, src, cluster, n0, beta, off, coef, cxi, sxi,
-                            cphi, sphi, psign, a, b, ceP, seP, ll, mm, nn1,
-                            rec),
-      entry_off, flux, r1, freqs, fdelta2, tdelta);
-  const int64_t R = s.a.rows.R, F = s.a.ch.F, M = s.tab.M;
-  TORCH_CHECK(out.device() == u.device() &&
-              out.scalar_type() == torch::kComplexFloat &&
-              out.is_contiguous() && out.numel() == (mean ? 1 : F) * M * R * 4
-              && out.dim() == (mean ? 3 : 4) && out.size(-2) == R,
+    py::dict tab_rec, torch::Tensor flux, torch::Tensor r1,
+    torch::Tensor freqs, double fdelta2, double tdelta, bool mean, int64_t K,
+    c10::optional<torch::Tensor> beam, c10::optional<torch::Tensor> ejones,
+    c10::optional<torch::Tensor> pairs, int64_t Nbase, int64_t Nsta_ej) {
+  const torch::Device dev = u.device();
+  const RowsUVW rows = rows_mf(u, v, w);
+  ShapeletTabMF tab = shapelet_tab_mf(tab_rec, u);
+  const Channels ch = channels(freqs, flux, r1, tab.t.S, fdelta2, tdelta, dev);
+  tab.t.flux = fp(flux); tab.t.r1 = fp(r1);
+  const int64_t R = rows.R, F = ch.F, M = tab.M;
+  TORCH_CHECK(on_dev(out, dev, torch::kComplexFloat,
+                     (mean ? 1 : F) * M * R * 4) &&
+              out.dim() == (mean ? 3 : 4) && out.size(-2) == R,
               "out must be contiguous [F, M, R, 4] complex64, or [M, R, 4] "
               "with mean");
   const BeamChannels bm = beam_channels(beam, ejones, pairs, Nbase, Nsta_ej,
-                                        s.a, K, u);
-  CHECK_HIP(launch_shapelet_coh_mf(s.a.rows, s.tab, s.a.ch, bm, mean ? 1 : 0,
-                                   cptr(out), cur_stream()));
+                                        R, F, K, dev);
+  CHECK_HIP(launch_shapelet_coh_mf(rows, tab, ch, bm, mean ? 1 : 0, cptr(out),
+                                   cur_stream()));
 }
 
 // Subtracts J_p C J_q^H of the shapelet sources of every cluster with
@@ -532,58 +523,27 @@ void shapelet_coh_channels_add(
 // chunk_tab, pairs, skip and the caller's guarantees as there.
 void shapelet_residuals_add(
     torch::Tensor out, torch::Tensor u, torch::Tensor v, torch::Tensor w,
-    torch::Tensor src, torch::Tensor cluster, torch::Tensor n0,
-    torch::Tensor beta, torch::Tensor off, torch::Tensor coef,
-    torch::Tensor cxi, torch::Tensor sxi, torch::Tensor cphi,
-    torch::Tensor sphi, torch::Tensor psign, torch::Tensor a,
-    torch::Tensor b, torch::Tensor ceP, torch::Tensor seP,
-    torch::Tensor ll, torch::Tensor mm, torch::Tensor nn1,
-    torch::Tensor rec, torch::Tensor entry_off, torch::Tensor flux,
-    torch::Tensor r1, torch::Tensor freqs, double fdelta2, double tdelta,
-    torch::Tensor J, torch::Tensor chunk_tab, torch::Tensor pairs,
+    py::dict tab_rec, torch::Tensor flux, torch::Tensor r1,
+    torch::Tensor freqs, double fdelta2, double tdelta, torch::Tensor J,
+    torch::Tensor chunk_tab, torch::Tensor pairs,
     c10::optional<torch::Tensor> skip, int64_t K,
     c10::optional<torch::Tensor> beam, c10::optional<torch::Tensor> ejones,
     int64_t Nsta_ej) {
-  const ShapeletMfArgs s = shapelet_mf_args(
-      u, v, w, shapelet_tab(u, src, cluster, n0, beta, off, coef, cxi, sxi,
-                            cphi, sphi, psign, a, b, ceP, seP, ll, mm, nn1,
-                            rec),
-      entry_off, flux, r1, freqs, fdelta2, tdelta);
-  const int64_t R = s.a.rows.R, F = s.a.ch.F, M = s.tab.M;
-  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType ty) {
-    return t.device() == u.device() && t.scalar_type() == ty &&
-           t.is_contiguous();
-  };
-  TORCH_CHECK(on_dev(out, torch::kComplexFloat) && out.dim() == 3 &&
+  const torch::Device dev = u.device();
+  const RowsUVW rows = rows_mf(u, v, w);
+  ShapeletTabMF tab = shapelet_tab_mf(tab_rec, u);
+  const Channels ch = channels(freqs, flux, r1, tab.t.S, fdelta2, tdelta, dev);
+  tab.t.flux = fp(flux); tab.t.r1 = fp(r1);
+  const int64_t R = rows.R, F = ch.F;
+  TORCH_CHECK(on_dev(out, dev, torch::kComplexFloat) && out.dim() == 3 &&
               out.size(0) == F && out.size(1) == R && out.size(2) == 4,
               "out must be contiguous [F, R, 4] complex64");
-  TORCH_CHECK(on_dev(J, torch::kComplexFloat) && J.dim() == 3 &&
-              J.size(0) >= 1 && J.size(1) >= 1 && J.size(2) == 4,
-              "J must be contiguous [Mt, N, 4] complex64");
-  TORCH_CHECK(on_dev(chunk_tab, torch::kInt) && chunk_tab.dim() == 2 &&
-              chunk_tab.size(0) == M && chunk_tab.size(1) >= 1,
-              "chunk_tab must be contiguous [M, T] int32");
-  TORCH_CHECK(on_dev(pairs, torch::kInt) && pairs.dim() == 2 &&
-              pairs.size(0) >= 1 && pairs.size(1) == 2,
-              "pairs must be contiguous [Nbase, 2] int32");
-  TORCH_CHECK(chunk_tab.size(1) * pairs.size(0) == R,
-              "rows must be T * Nbase");
-  ResidualArgs res = {};
-  res.J = ccptr(J);
-  res.chunk_tab = ip(chunk_tab);
-  res.pairs = ip(pairs);
-  if (skip.has_value()) {
-    TORCH_CHECK(on_dev(*skip, torch::kInt) && skip->numel() == M,
-                "skip must be contiguous [M] int32");
-    res.skip = ip(*skip);
-  }
-  res.Nbase = (int)pairs.size(0);
-  res.T = (int)chunk_tab.size(1);
-  res.N = (int)J.size(1);
+  const ResidualArgs res = residual_args(J, chunk_tab, pairs, skip, tab.M, R,
+                                         dev);
   const BeamChannels bm = beam_channels(beam, ejones, pairs, pairs.size(0),
-                                        Nsta_ej, s.a, K, u);
-  CHECK_HIP(launch_shapelet_residual_mf(s.a.rows, s.tab, s.a.ch, bm, res,
-                                        cptr(out), cur_stream()));
+                                        Nsta_ej, R, F, K, dev);
+  CHECK_HIP(launch_shapelet_residual_mf(rows, tab, ch, bm, res, cptr(out),
+                                        cur_stream()));
 }
 
 // The four tensors both beam-gain entry points share: elem [N, Emax, 3]
@@ -592,21 +552,16 @@ void shapelet_residuals_add(
 static void check_beam_geometry(
     const torch::Tensor& elem, const torch::Tensor& nelem,
     const torch::Tensor& du, const torch::Tensor& below) {
-  TORCH_CHECK(elem.is_cuda() && elem.scalar_type() == torch::kDouble &&
-              elem.is_contiguous() && elem.dim() == 3 && elem.size(2) == 3 &&
-              elem.size(1) > 0, "elem must be contiguous [N, Emax, 3] float64");
-  TORCH_CHECK(nelem.device() == elem.device() &&
-              nelem.scalar_type() == torch::kInt && nelem.is_contiguous() &&
-              nelem.numel() == elem.size(0),
+  const torch::Device dev = elem.device();
+  TORCH_CHECK(on_dev(elem, dev, torch::kDouble) && elem.dim() == 3 &&
+              elem.size(2) == 3 && elem.size(1) > 0,
+              "elem must be contiguous [N, Emax, 3] float64");
+  TORCH_CHECK(on_dev(nelem, dev, torch::kInt, elem.size(0)),
               "nelem must be contiguous [N] int32");
-  TORCH_CHECK(du.device() == elem.device() &&
-              du.scalar_type() == torch::kDouble && du.is_contiguous() &&
-              du.dim() == 3 && du.size(2) == 3,
-              "du must be contiguous [T, K, 3] float64");
-  TORCH_CHECK(below.device() == elem.device() &&
-              below.scalar_type() == torch::kByte && below.is_contiguous() &&
-              below.dim() == 2 && below.size(0) == du.size(0) &&
-              below.size(1) == du.size(1),
+  TORCH_CHECK(on_dev(du, dev, torch::kDouble) && du.dim() == 3 &&
+              du.size(2) == 3, "du must be contiguous [T, K, 3] float64");
+  TORCH_CHECK(on_dev(below, dev, torch::kByte) && below.dim() == 2 &&
+              below.size(0) == du.size(0) && below.size(1) == du.size(1),
               "below must be contiguous [T, K] uint8");
   TORCH_CHECK(du.size(0) * du.size(1) < (int64_t(1) << 31),
               "too many (timeslot, source) pairs");
@@ -638,11 +593,11 @@ torch::Tensor station_beam_gains(
     torch::Tensor below, torch::Tensor kf,
     c10::optional<torch::Tensor> tile, c10::optional<torch::Tensor> du_tile) {
   check_beam_geometry(elem, nelem, du, below);
+  const torch::Device dev = elem.device();
   const int64_t N = elem.size(0), Emax = elem.size(1);
   const int64_t T = du.size(0), K = du.size(1);
-  TORCH_CHECK(kf.device() == elem.device() &&
-              kf.scalar_type() == torch::kDouble && kf.is_contiguous() &&
-              kf.dim() == 1, "kf must be contiguous [F] float64");
+  TORCH_CHECK(on_dev(kf, dev, torch::kDouble) && kf.dim() == 1,
+              "kf must be contiguous [F] float64");
   const int64_t F = kf.size(0);
   TORCH_CHECK(tile.has_value() == du_tile.has_value(),
               "tile and du_tile come together");
@@ -652,22 +607,19 @@ torch::Tensor station_beam_gains(
   if (tile.has_value()) {
     const torch::Tensor& tl = *tile;
     const torch::Tensor& dt = *du_tile;
-    TORCH_CHECK(tl.device() == elem.device() &&
-                tl.scalar_type() == torch::kDouble && tl.is_contiguous() &&
-                tl.dim() == 3 && tl.size(0) == N && tl.size(2) == 3 &&
-                tl.size(1) >= 1 && tl.size(1) <= 64,
+    TORCH_CHECK(on_dev(tl, dev, torch::kDouble) && tl.dim() == 3 &&
+                tl.size(0) == N && tl.size(2) == 3 && tl.size(1) >= 1 &&
+                tl.size(1) <= 64,
                 "tile must be contiguous [N, D, 3] float64, 1 <= D <= 64");
-    TORCH_CHECK(dt.device() == elem.device() &&
-                dt.scalar_type() == torch::kDouble && dt.is_contiguous() &&
-                dt.dim() == 3 && dt.size(0) == T && dt.size(1) == K &&
-                dt.size(2) == 3,
+    TORCH_CHECK(on_dev(dt, dev, torch::kDouble) && dt.dim() == 3 &&
+                dt.size(0) == T && dt.size(1) == K && dt.size(2) == 3,
                 "du_tile must be contiguous [T, K, 3] float64");
     D = tl.size(1);
     tile_p = tl.data_ptr<double>();
     dut_p = dt.data_ptr<double>();
   }
   auto gain = torch::empty({F, T, K, N},
-      torch::dtype(torch::kFloat).device(elem.device()));
+      torch::dtype(torch::kFloat).device(dev));
   CHECK_HIP(launch_station_beam(elem.data_ptr<double>(),
       nelem.data_ptr<int>(), tile_p, du.data_ptr<double>(), dut_p,
       below.data_ptr<uint8_t>(), kf.data_ptr<double>(), (int)N, (int)Emax,
@@ -686,28 +638,24 @@ torch::Tensor element_jones(
               ELEMENT_BEAM_MAX_M, ", got ", M);
   TORCH_CHECK(beta > 0.0 && (float)beta > 0.f, "beta must be positive");
   const int64_t Nmodes = M * (M + 1) / 2;
-  TORCH_CHECK(az.is_cuda() && az.scalar_type() == torch::kDouble &&
-              az.is_contiguous() && az.dim() == 1,
+  const torch::Device dev = az.device();
+  TORCH_CHECK(on_dev(az, dev, torch::kDouble) && az.dim() == 1,
               "az must be contiguous [D] float64 on the device");
-  TORCH_CHECK(el.device() == az.device() &&
-              el.scalar_type() == torch::kDouble && el.is_contiguous() &&
-              el.dim() == 1 && el.size(0) == az.size(0),
+  TORCH_CHECK(on_dev(el, dev, torch::kDouble) && el.dim() == 1 &&
+              el.size(0) == az.size(0),
               "el must be contiguous [D] float64 like az");
-  TORCH_CHECK(coef.device() == az.device() &&
-              coef.scalar_type() == torch::kComplexFloat &&
-              coef.is_contiguous() && coef.dim() == 3 && coef.size(0) >= 1 &&
-              coef.size(1) == 2 && coef.size(2) == Nmodes,
+  TORCH_CHECK(on_dev(coef, dev, torch::kComplexFloat) && coef.dim() == 3 &&
+              coef.size(0) >= 1 && coef.size(1) == 2 &&
+              coef.size(2) == Nmodes,
               "coef must be contiguous [F, 2, M(M+1)/2] complex64, F >= 1");
-  TORCH_CHECK(preamble.device() == az.device() &&
-              preamble.scalar_type() == torch::kFloat &&
-              preamble.is_contiguous() && preamble.dim() == 1 &&
+  TORCH_CHECK(on_dev(preamble, dev, torch::kFloat) && preamble.dim() == 1 &&
               preamble.size(0) == Nmodes,
               "preamble must be contiguous [M(M+1)/2] float32");
   const int64_t D = az.size(0), F = coef.size(0);
   TORCH_CHECK(D < (int64_t(1) << 31) && F < (int64_t(1) << 31),
               "too many directions or frequencies");
   auto E = torch::empty({F, D, 2, 2},
-      torch::dtype(torch::kComplexFloat).device(az.device()));
+      torch::dtype(torch::kComplexFloat).device(dev));
   CHECK_HIP(launch_element_beam(az.data_ptr<double>(), el.data_ptr<double>(),
       ccptr(coef), preamble.data_ptr<float>(), (int)D, (int)F, (int)M,
       (float)beta, cptr(E), cur_stream()));
@@ -859,48 +807,33 @@ std::vector<torch::Tensor> lbfgs_cost_grad_channels(
     torch::Tensor chunk_tab, torch::Tensor pairs, torch::Tensor ext,
     torch::Tensor ext_off, torch::Tensor sta_off, torch::Tensor sta_ent,
     double robust_nu) {
-  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType ty) {
-    return t.is_cuda() && t.device() == xs.device() &&
-           t.scalar_type() == ty && t.is_contiguous();
-  };
-  TORCH_CHECK(on_dev(xs, torch::kComplexFloat) && xs.dim() == 3 &&
+  const torch::Device dev = xs.device();
+  TORCH_CHECK(on_dev(xs, dev, torch::kComplexFloat) && xs.dim() == 3 &&
               xs.size(0) >= 1 && xs.size(1) >= 1 && xs.size(2) == 4,
               "xs must be contiguous [F, R, 4] complex64 on the device");
   const int64_t F = xs.size(0), R = xs.size(1);
-  TORCH_CHECK(on_dev(cohs, torch::kComplexFloat) && cohs.dim() == 4 &&
+  TORCH_CHECK(on_dev(cohs, dev, torch::kComplexFloat) && cohs.dim() == 4 &&
               cohs.size(0) == F && cohs.size(1) >= 1 && cohs.size(2) == R &&
               cohs.size(3) == 4,
               "cohs must be contiguous [F, M, R, 4] complex64");
   const int64_t M = cohs.size(1);
-  TORCH_CHECK(on_dev(J, torch::kComplexFloat) && J.dim() == 3 &&
-              J.size(0) >= 1 && J.size(1) >= 1 && J.size(2) == 4,
-              "J must be contiguous [Mt, N, 4] complex64");
+  check_solution_tables(J, chunk_tab, pairs, M, R, dev);
   const int64_t Mt = J.size(0), N = J.size(1);
-  TORCH_CHECK(on_dev(chunk_tab, torch::kInt) && chunk_tab.dim() == 2 &&
-              chunk_tab.size(0) == M && chunk_tab.size(1) >= 1,
-              "chunk_tab must be contiguous [M, T] int32");
-  TORCH_CHECK(on_dev(pairs, torch::kInt) && pairs.dim() == 2 &&
-              pairs.size(0) >= 1 && pairs.size(1) == 2,
-              "pairs must be contiguous [Nbase, 2] int32");
   const int64_t T = chunk_tab.size(1), Nbase = pairs.size(0);
-  TORCH_CHECK(T * Nbase == R && R < (int64_t(1) << 31),
-              "rows must be T * Nbase, below 2^31");
-  TORCH_CHECK(on_dev(ext, torch::kInt) && ext.dim() == 2 &&
+  TORCH_CHECK(on_dev(ext, dev, torch::kInt) && ext.dim() == 2 &&
               ext.size(0) >= 1 && ext.size(1) == 4,
               "ext must be contiguous [E, 4] int32");
   const int64_t E = ext.size(0);
-  TORCH_CHECK(on_dev(ext_off, torch::kInt) && ext_off.numel() == Mt + 1,
+  TORCH_CHECK(on_dev(ext_off, dev, torch::kInt, Mt + 1),
               "ext_off must be contiguous [Mt + 1] int32");
-  TORCH_CHECK(on_dev(sta_off, torch::kInt) && sta_off.numel() == N + 1,
+  TORCH_CHECK(on_dev(sta_off, dev, torch::kInt, N + 1),
               "sta_off must be contiguous [N + 1] int32");
-  TORCH_CHECK(on_dev(sta_ent, torch::kInt) && sta_ent.numel() <= 2 * Nbase,
+  TORCH_CHECK(on_dev(sta_ent, dev, torch::kInt) &&
+              sta_ent.numel() <= 2 * Nbase,
               "sta_ent must be contiguous int32, at most 2 * Nbase entries");
   TORCH_CHECK(E < (int64_t(1) << 31) / Nbase && Mt * N < (int64_t(1) << 28),
               "too many extents or parameters");
-  // the kernels read 2x2 matrices as two 16-byte loads
-  for (const torch::Tensor* t : {&xs, &cohs, &J})
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
-                "xs, cohs and J must be 16-byte aligned");
+  check_aligned16({&xs, &cohs, &J}, "xs, cohs and J");
   LbfgsMfArgs a = {};
   a.xs = ccptr(xs); a.cohs = ccptr(cohs); a.J = ccptr(J);
   a.pairs = ip(pairs); a.chunk_tab = ip(chunk_tab);
@@ -909,8 +842,8 @@ std::vector<torch::Tensor> lbfgs_cost_grad_channels(
   a.F = (int)F; a.M = (int)M; a.T = (int)T; a.Nbase = (int)Nbase;
   a.N = (int)N; a.Mt = (int)Mt; a.E = (int)E;
   a.nu = (float)robust_nu;
-  auto fopts = torch::dtype(torch::kFloat).device(xs.device());
-  auto copts = torch::dtype(torch::kComplexFloat).device(xs.device());
+  auto fopts = torch::dtype(torch::kFloat).device(dev);
+  auto copts = torch::dtype(torch::kComplexFloat).device(dev);
   auto sres = torch::empty({F, R, 4}, copts);
   auto slots = torch::empty({E, Nbase, 8}, copts);
   auto cpart = torch::empty({F * ((R + LBFGS_MF_TB - 1) / LBFGS_MF_TB)},
@@ -939,46 +872,30 @@ std::vector<torch::Tensor> joint_jtj(
     torch::Tensor gtab, torch::Tensor cbin, torch::Tensor sdst,
     torch::Tensor gdst, torch::Tensor cpos, torch::Tensor sta_off,
     torch::Tensor sta_ent, int64_t nblk, int64_t nbin, bool cost_only) {
-  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType ty) {
-    return t.is_cuda() && t.device() == x.device() &&
-           t.scalar_type() == ty && t.is_contiguous();
-  };
-  TORCH_CHECK(on_dev(x, torch::kComplexFloat) && x.dim() == 2 &&
+  const torch::Device dev = x.device();
+  TORCH_CHECK(on_dev(x, dev, torch::kComplexFloat) && x.dim() == 2 &&
               x.size(0) >= 1 && x.size(1) == 4,
               "x must be contiguous [R, 4] complex64 on the device");
   const int64_t R = x.size(0);
-  TORCH_CHECK(on_dev(cohs, torch::kComplexFloat) && cohs.dim() == 3 &&
+  TORCH_CHECK(on_dev(cohs, dev, torch::kComplexFloat) && cohs.dim() == 3 &&
               cohs.size(0) >= 1 && cohs.size(1) == R && cohs.size(2) == 4,
               "cohs must be contiguous [M, R, 4] complex64");
   const int64_t M = cohs.size(0);
-  TORCH_CHECK(on_dev(J, torch::kComplexFloat) && J.dim() == 3 &&
-              J.size(0) >= 1 && J.size(1) >= 1 && J.size(2) == 4,
-              "J must be contiguous [Mt, N, 4] complex64");
-  const int64_t Mt = J.size(0), N = J.size(1);
-  TORCH_CHECK(!wts.has_value() ||
-              (on_dev(*wts, torch::kFloat) && wts->numel() == R),
+  TORCH_CHECK(!wts.has_value() || on_dev(*wts, dev, torch::kFloat, R),
               "weights must be contiguous [R] float32");
-  TORCH_CHECK(on_dev(chunk_tab, torch::kInt) && chunk_tab.dim() == 2 &&
-              chunk_tab.size(0) == M && chunk_tab.size(1) >= 1,
-              "chunk_tab must be contiguous [M, T] int32");
-  TORCH_CHECK(on_dev(pairs, torch::kInt) && pairs.dim() == 2 &&
-              pairs.size(0) >= 1 && pairs.size(1) == 2,
-              "pairs must be contiguous [Nbase, 2] int32");
+  check_solution_tables(J, chunk_tab, pairs, M, R, dev);
+  const int64_t Mt = J.size(0), N = J.size(1);
   const int64_t T = chunk_tab.size(1), Nbase = pairs.size(0);
-  TORCH_CHECK(T * Nbase == R && R < (int64_t(1) << 31),
-              "rows must be T * Nbase, below 2^31");
-  TORCH_CHECK(on_dev(pieces, torch::kInt) && pieces.dim() == 2 &&
+  TORCH_CHECK(on_dev(pieces, dev, torch::kInt) && pieces.dim() == 2 &&
               pieces.size(0) >= 1 && pieces.size(1) == 2,
               "pieces must be contiguous [E, 2] int32");
   const int64_t E = pieces.size(0), ntri = M * (M + 1) / 2;
-  TORCH_CHECK(on_dev(cbin, torch::kInt) && cbin.numel() == E,
+  TORCH_CHECK(on_dev(cbin, dev, torch::kInt, E),
               "cbin must be contiguous [E] int32");
   TORCH_CHECK(nblk >= 1 && Mt % nblk == 0 && nbin >= 1,
               "Mt must be a multiple of the block count");
   TORCH_CHECK(Mt * N < (int64_t(1) << 27), "too many parameters");
-  for (const torch::Tensor* t : {&x, &cohs, &J})
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
-                "x, cohs and J must be 16-byte aligned");
+  check_aligned16({&x, &cohs, &J}, "x, cohs and J");
   JointJtjArgs a = {};
   a.x = ccptr(x); a.cohs = ccptr(cohs); a.J = ccptr(J);
   a.wts = wts.has_value() ? wts->data_ptr<float>() : nullptr;
@@ -987,8 +904,8 @@ std::vector<torch::Tensor> joint_jtj(
   a.M = (int)M; a.T = (int)T; a.Nbase = (int)Nbase; a.N = (int)N;
   a.Mt = (int)Mt; a.E = (int)E; a.nbin = (int)nbin;
   a.ld = 8 * N * (Mt / nblk);
-  auto fopts = torch::dtype(torch::kFloat).device(x.device());
-  auto copts = torch::dtype(torch::kComplexFloat).device(x.device());
+  auto fopts = torch::dtype(torch::kFloat).device(dev);
+  auto copts = torch::dtype(torch::kComplexFloat).device(dev);
   auto PC = torch::empty({Nbase, E}, fopts);
   auto cost = torch::empty({nbin}, fopts);
   if (cost_only) {
@@ -996,20 +913,21 @@ std::vector<torch::Tensor> joint_jtj(
                                 cost.data_ptr<float>(), cur_stream()));
     return {cost};
   }
-  TORCH_CHECK(on_dev(etab, torch::kInt) && etab.numel() == E * ntri,
+  TORCH_CHECK(on_dev(etab, dev, torch::kInt, E * ntri),
               "etab must be contiguous [E, M(M+1)/2] int32");
-  TORCH_CHECK(on_dev(gtab, torch::kInt) && gtab.numel() == E * M,
+  TORCH_CHECK(on_dev(gtab, dev, torch::kInt, E * M),
               "gtab must be contiguous [E, M] int32");
-  TORCH_CHECK(on_dev(sdst, torch::kInt) && sdst.dim() == 2 &&
+  TORCH_CHECK(on_dev(sdst, dev, torch::kInt) && sdst.dim() == 2 &&
               sdst.size(0) >= 1 && sdst.size(1) == 2,
               "sdst must be contiguous [D, 2] int32");
-  TORCH_CHECK(on_dev(gdst, torch::kInt) && gdst.numel() >= 1 &&
+  TORCH_CHECK(on_dev(gdst, dev, torch::kInt) && gdst.numel() >= 1 &&
               gdst.numel() <= Mt, "gdst must be contiguous [G] int32");
-  TORCH_CHECK(on_dev(cpos, torch::kInt) && cpos.numel() == 2 * Mt,
+  TORCH_CHECK(on_dev(cpos, dev, torch::kInt, 2 * Mt),
               "cpos must be contiguous [Mt, 2] int32");
-  TORCH_CHECK(on_dev(sta_off, torch::kInt) && sta_off.numel() == N + 1,
+  TORCH_CHECK(on_dev(sta_off, dev, torch::kInt, N + 1),
               "sta_off must be contiguous [N + 1] int32");
-  TORCH_CHECK(on_dev(sta_ent, torch::kInt) && sta_ent.numel() <= 2 * Nbase,
+  TORCH_CHECK(on_dev(sta_ent, dev, torch::kInt) &&
+              sta_ent.numel() <= 2 * Nbase,
               "sta_ent must be contiguous int32, at most 2 * Nbase entries");
   a.etab = ip(etab); a.gtab = ip(gtab); a.sdst = ip(sdst); a.gdst = ip(gdst);
   a.cpos = ip(cpos); a.sta_off = ip(sta_off); a.sta_ent = ip(sta_ent);
@@ -1030,31 +948,26 @@ std::vector<torch::Tensor> joint_jtj(
 std::vector<torch::Tensor> rtr_tcg(
     torch::Tensor JtJ, torch::Tensor Jtr, torch::Tensor J, torch::Tensor iw,
     torch::Tensor delta, int64_t maxit, double kappa) {
-  auto on_dev = [&](const torch::Tensor& t, torch::ScalarType ty) {
-    return t.is_cuda() && t.device() == JtJ.device() &&
-           t.scalar_type() == ty && t.is_contiguous();
-  };
-  TORCH_CHECK(on_dev(J, torch::kComplexFloat) && J.dim() == 4 &&
+  const torch::Device dev = JtJ.device();
+  TORCH_CHECK(on_dev(J, dev, torch::kComplexFloat) && J.dim() == 4 &&
               J.size(0) >= 1 && J.size(2) == 2 && J.size(3) == 2,
               "J must be contiguous [n, N, 2, 2] complex64 on the device");
   const int64_t n = J.size(0), N = J.size(1), P = 8 * N;
   TORCH_CHECK(N >= 2 && P <= RTR_TCG_MAXP && n < (int64_t(1) << 31),
               "rtr_tcg takes 2 <= N <= ", RTR_TCG_MAXP / 8, " stations");
-  TORCH_CHECK(on_dev(JtJ, torch::kFloat) && JtJ.dim() == 3 &&
+  TORCH_CHECK(on_dev(JtJ, dev, torch::kFloat) && JtJ.dim() == 3 &&
               JtJ.size(0) == n && JtJ.size(1) == P && JtJ.size(2) == P,
               "JtJ must be contiguous [n, 8N, 8N] float32");
-  TORCH_CHECK(on_dev(Jtr, torch::kFloat) && Jtr.dim() == 2 &&
+  TORCH_CHECK(on_dev(Jtr, dev, torch::kFloat) && Jtr.dim() == 2 &&
               Jtr.size(0) == n && Jtr.size(1) == P,
               "Jtr must be contiguous [n, 8N] float32");
-  TORCH_CHECK(on_dev(iw, torch::kFloat) && iw.dim() == 1 && iw.size(0) == N,
-              "iw must be contiguous [N] float32");
-  TORCH_CHECK(on_dev(delta, torch::kFloat) && delta.dim() == 1 &&
+  TORCH_CHECK(on_dev(iw, dev, torch::kFloat) && iw.dim() == 1 &&
+              iw.size(0) == N, "iw must be contiguous [N] float32");
+  TORCH_CHECK(on_dev(delta, dev, torch::kFloat) && delta.dim() == 1 &&
               delta.size(0) == n, "delta must be contiguous [n] float32");
   TORCH_CHECK(maxit >= 0 && maxit < (int64_t(1) << 24),
               "maxit must be in 0 .. 2^24");
-  for (const torch::Tensor* t : {&JtJ, &Jtr, &J})
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
-                "JtJ, Jtr and J must be 16-byte aligned");
+  check_aligned16({&JtJ, &Jtr, &J}, "JtJ, Jtr and J");
   RtrTcgArgs a = {};
   a.JtJ = fp(JtJ); a.Jtr = fp(Jtr); a.J = ccptr(J); a.iw = fp(iw);
   a.delta = fp(delta);
@@ -1088,62 +1001,45 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("chol_solve", &chol_solve, "batched damped Cholesky solve (gfx950)");
   m.def("chol_solve_mw", &chol_solve_mw,
         "multi-workgroup damped Cholesky solve (gfx950)");
+  // The predict entry points take the per-source arrays as the record `src`
+  // (hip_host.GPUPack.record) or the shapelet mode table as the record
+  // `tab` (hip_host.ShapeletTable.record), dicts from field name to tensor.
   m.def("predict_coh", &predict_coh, "coherency predict (gfx950)",
-        py::arg("u"), py::arg("v"), py::arg("w"), py::arg("ll"),
-        py::arg("mm"), py::arg("nn1"), py::arg("sI"), py::arg("sQ"),
-        py::arg("sU"), py::arg("sV"), py::arg("eX"), py::arg("eY"),
-        py::arg("eP"), py::arg("cxi"), py::arg("sxi"), py::arg("cphi"),
-        py::arg("sphi"), py::arg("r1"), py::arg("stype"),
-        py::arg("cluster_off"), py::arg("freq"), py::arg("fdelta2"),
+        py::arg("u"), py::arg("v"), py::arg("w"), py::arg("src"),
+        py::arg("flux"), py::arg("r1"), py::arg("freq"), py::arg("fdelta2"),
         py::arg("tdelta"), py::arg("beam") = py::none(),
         py::arg("pairs") = py::none(), py::arg("Nbase") = 0,
         py::arg("ejones") = py::none(), py::arg("Nsta") = 0);
   m.def("shapelet_coh_add", &shapelet_coh_add,
         "add shapelet-source coherencies into out (gfx950)",
         py::arg("out"), py::arg("u"), py::arg("v"), py::arg("w"),
-        py::arg("src"), py::arg("cluster"), py::arg("n0"), py::arg("beta"),
-        py::arg("off"), py::arg("coef"), py::arg("cxi"), py::arg("sxi"),
-        py::arg("cphi"), py::arg("sphi"), py::arg("psign"), py::arg("a"),
-        py::arg("b"), py::arg("ceP"), py::arg("seP"), py::arg("ll"),
-        py::arg("mm"), py::arg("nn1"), py::arg("rec"), py::arg("flux"),
-        py::arg("r1"), py::arg("freq"), py::arg("fdelta2"),
-        py::arg("tdelta"), py::arg("beam") = py::none(),
+        py::arg("tab"), py::arg("flux"), py::arg("r1"), py::arg("freq"),
+        py::arg("fdelta2"), py::arg("tdelta"), py::arg("beam") = py::none(),
         py::arg("pairs") = py::none(), py::arg("Nbase") = 0,
         py::arg("ejones") = py::none(), py::arg("Nsta") = 0);
   m.def("predict_coh_channels", &predict_coh_channels,
         "coherency predict, all channels in one launch (gfx950)",
-        py::arg("u"), py::arg("v"), py::arg("w"), py::arg("ll"),
-        py::arg("mm"), py::arg("nn1"), py::arg("flux"), py::arg("eX"),
-        py::arg("eY"), py::arg("eP"), py::arg("cxi"), py::arg("sxi"),
-        py::arg("cphi"), py::arg("sphi"), py::arg("r1"), py::arg("stype"),
-        py::arg("cluster_off"), py::arg("freqs"), py::arg("fdelta2"),
+        py::arg("u"), py::arg("v"), py::arg("w"), py::arg("src"),
+        py::arg("flux"), py::arg("r1"), py::arg("freqs"), py::arg("fdelta2"),
         py::arg("tdelta"), py::arg("mean") = false,
         py::arg("beam") = py::none(), py::arg("ejones") = py::none(),
         py::arg("pairs") = py::none(), py::arg("Nbase") = 0,
         py::arg("Nsta") = 0);
   m.def("residuals_multifreq", &residuals_multifreq,
         "predict and subtract, all channels in one launch (gfx950)",
-        py::arg("x"), py::arg("u"), py::arg("v"), py::arg("w"), py::arg("ll"),
-        py::arg("mm"), py::arg("nn1"), py::arg("flux"), py::arg("eX"),
-        py::arg("eY"), py::arg("eP"), py::arg("cxi"), py::arg("sxi"),
-        py::arg("cphi"), py::arg("sphi"), py::arg("r1"), py::arg("stype"),
-        py::arg("cluster_off"), py::arg("freqs"), py::arg("fdelta2"),
-        py::arg("tdelta"), py::arg("J"), py::arg("chunk_tab"),
-        py::arg("pairs"), py::arg("skip") = py::none(),
-        py::arg("beam") = py::none(), py::arg("ejones") = py::none(),
-        py::arg("Nsta") = 0);
+        py::arg("x"), py::arg("u"), py::arg("v"), py::arg("w"),
+        py::arg("src"), py::arg("flux"), py::arg("r1"), py::arg("freqs"),
+        py::arg("fdelta2"), py::arg("tdelta"), py::arg("J"),
+        py::arg("chunk_tab"), py::arg("pairs"),
+        py::arg("skip") = py::none(), py::arg("beam") = py::none(),
+        py::arg("ejones") = py::none(), py::arg("Nsta") = 0);
   m.attr("PREDICT_MF_NF") = PREDICT_MF_NF;
   m.attr("PREDICT_MF_NF_EJ") = PREDICT_MF_NF_EJ;
   m.def("shapelet_coh_channels_add", &shapelet_coh_channels_add,
         "add shapelet-source coherencies of all channels into out (gfx950)",
         py::arg("out"), py::arg("u"), py::arg("v"), py::arg("w"),
-        py::arg("src"), py::arg("cluster"), py::arg("n0"), py::arg("beta"),
-        py::arg("off"), py::arg("coef"), py::arg("cxi"), py::arg("sxi"),
-        py::arg("cphi"), py::arg("sphi"), py::arg("psign"), py::arg("a"),
-        py::arg("b"), py::arg("ceP"), py::arg("seP"), py::arg("ll"),
-        py::arg("mm"), py::arg("nn1"), py::arg("rec"), py::arg("entry_off"),
-        py::arg("flux"), py::arg("r1"), py::arg("freqs"), py::arg("fdelta2"),
-        py::arg("tdelta"), py::arg("mean"), py::arg("K"),
+        py::arg("tab"), py::arg("flux"), py::arg("r1"), py::arg("freqs"),
+        py::arg("fdelta2"), py::arg("tdelta"), py::arg("mean"), py::arg("K"),
         py::arg("beam") = py::none(), py::arg("ejones") = py::none(),
         py::arg("pairs") = py::none(), py::arg("Nbase") = 0,
         py::arg("Nsta") = 0);
@@ -1151,14 +1047,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "subtract the shapelet-source model of all channels from out "
         "(gfx950)",
         py::arg("out"), py::arg("u"), py::arg("v"), py::arg("w"),
-        py::arg("src"), py::arg("cluster"), py::arg("n0"), py::arg("beta"),
-        py::arg("off"), py::arg("coef"), py::arg("cxi"), py::arg("sxi"),
-        py::arg("cphi"), py::arg("sphi"), py::arg("psign"), py::arg("a"),
-        py::arg("b"), py::arg("ceP"), py::arg("seP"), py::arg("ll"),
-        py::arg("mm"), py::arg("nn1"), py::arg("rec"), py::arg("entry_off"),
-        py::arg("flux"), py::arg("r1"), py::arg("freqs"), py::arg("fdelta2"),
-        py::arg("tdelta"), py::arg("J"), py::arg("chunk_tab"),
-        py::arg("pairs"), py::arg("skip"), py::arg("K"),
+        py::arg("tab"), py::arg("flux"), py::arg("r1"), py::arg("freqs"),
+        py::arg("fdelta2"), py::arg("tdelta"), py::arg("J"),
+        py::arg("chunk_tab"), py::arg("pairs"), py::arg("skip"), py::arg("K"),
         py::arg("beam") = py::none(), py::arg("ejones") = py::none(),
         py::arg("Nsta") = 0);
   m.attr("SHAPELET_MF_NF") = SHAPELET_MF_NF;

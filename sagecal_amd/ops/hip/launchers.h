@@ -29,8 +29,9 @@ struct SourceArrays {
   int M;
 };
 
-// Shapelet mode table of k_shapelet_coh, S entries; the pointers in
-// hip_host.ShapeletTable.FIELDS order, then what changes per call.
+// Shapelet mode table of k_shapelet_coh, S entries; the fields the binding
+// looks up by name in hip_host.ShapeletTable.record, then what changes per
+// call.
 struct ShapeletTab {
   const int *src, *cluster, *n0;
   const float* beta;

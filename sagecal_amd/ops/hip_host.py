@@ -53,8 +53,11 @@ class ShapeletTable:
                          sqrt(2/n), sqrt((n-1)/n); rec[:,0] unused
       entry_off          int32 [M+1]  entries of cluster ci at
                          entry_off[ci] <= s < entry_off[ci+1]; read by the
-                         all-channels kernels only and not in FIELDS, the
-                         positional arguments of shapelet_coh_add
+                         all-channels kernels only
+
+    These are FIELDS, and `record` maps each name to its tensor: the `tab`
+    argument of the extension's shapelet entry points, which look the
+    fields up by name (SHAPELET_FIELDS in bindings.cpp).
 
     `float` is float32, the kernel's layout; dtype=torch.float64 keeps the
     host-computed values unrounded for fp64 checks of the mirror. The
@@ -63,10 +66,9 @@ class ShapeletTable:
 
     FIELDS = ('src', 'cluster', 'n0', 'beta', 'off', 'coef', 'cxi', 'sxi',
               'cphi', 'sphi', 'psign', 'a', 'b', 'ceP', 'seP', 'll', 'mm',
-              'nn1', 'rec')
+              'nn1', 'rec', 'entry_off')
 
     def __init__(self, pack, device, dtype=torch.float32):
-        import numpy as np
         items = sorted(pack.shapelets.items())
         src = np.array([g for g, _ in items], dtype=np.int64)
         host = lambda t: t.detach().cpu().to(torch.float64).numpy()[src]
@@ -123,6 +125,7 @@ class ShapeletTable:
         self.mm = flt(host(pack.mm), torch.float64)
         self.nn1 = flt(host(pack.nn1), torch.float64)
         self.rec = flt(rec)
+        self.record = {k: getattr(self, k) for k in self.FIELDS}
         self.cluster_long = self.cluster.long()
         self.src_long = self.src.long()
         self.pad_idx = torch.as_tensor(
@@ -198,7 +201,14 @@ def shapelet_coh_torch(tab, flux, r1, u, v, w, freq, fdelta, tdelta,
 
 class GPUPack:
     """Device-resident SourcePack in kernel layout (float32 props, float64
-    direction cosines, projection identity baked for use_proj=False)."""
+    direction cosines, projection identity baked for use_proj=False).
+    `record` maps each name of FIELDS to its tensor: the `src` argument of
+    the extension's predict entry points, which look the fields up by name
+    (SOURCE_FIELDS in bindings.cpp). The fluxes are [4, K] stacks of the I,
+    Q, U, V rows: `flux` at freq0 and `flux0` at the catalogue f0."""
+
+    FIELDS = ('ll', 'mm', 'nn1', 'eX', 'eY', 'eP', 'cxi', 'sxi', 'cphi',
+              'sphi', 'stype', 'cluster_off')
 
     def __init__(self, pack, device):
         f32 = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
@@ -206,9 +216,11 @@ class GPUPack:
         self.M = pack.M
         self.K = int(pack.cluster_off[-1])       # sources in the pack
         self.ll, self.mm, self.nn1 = f64(pack.ll), f64(pack.mm), f64(pack.nn1)
-        for k in ('sI', 'sQ', 'sU', 'sV', 'sI0', 'sQ0', 'sU0', 'sV0',
-                  'spec_idx', 'spec_idx1', 'spec_idx2', 'eX', 'eY', 'eP'):
+        for k in ('spec_idx', 'spec_idx1', 'spec_idx2', 'eX', 'eY', 'eP'):
             setattr(self, k, f32(getattr(pack, k)))
+        stack = lambda ks: torch.stack([f32(getattr(pack, k)) for k in ks])
+        self.flux = stack(('sI', 'sQ', 'sU', 'sV'))
+        self.flux0 = stack(('sI0', 'sQ0', 'sU0', 'sV0'))
         self.f0 = pack.f0.to(device=device, dtype=torch.float64)
         # gaussian honors use_projection; disk/ring ALWAYS project
         # (disk_contrib/ring_contrib predict.c:60-90, oracle-verified)
@@ -225,29 +237,21 @@ class GPUPack:
         # shapelet sources go through k_shapelet_coh from the table below:
         # zero their fluxes in the main-kernel arrays so they contribute
         # nothing there, and keep the true ones gathered per table entry
-        self.sh = None
+        self.sh = self._sh_flux = self._sh_flux0 = None
         if getattr(pack, 'shapelets', None):
             self.sh = ShapeletTable(pack, device)
-            src = self.sh.src
-            gather = lambda ks: torch.stack(
-                [getattr(self, k).index_select(0, src) for k in ks]
-            ).contiguous()
-            self._sh_flux = gather(('sI', 'sQ', 'sU', 'sV'))        # [4,S]
-            self._sh_flux0 = gather(('sI0', 'sQ0', 'sU0', 'sV0'))
-            sh = self.stype == 4
-            for k in ('sI', 'sQ', 'sU', 'sV', 'sI0', 'sQ0', 'sU0', 'sV0'):
-                t = getattr(self, k).clone()
-                t[sh] = 0.0
-                setattr(self, k, t.contiguous())
+            self._sh_flux = self.flux.index_select(1, self.sh.src)  # [4,S]
+            self._sh_flux0 = self.flux0.index_select(1, self.sh.src)
+            self.flux[:, self.stype == 4] = 0.0
+            self.flux0[:, self.stype == 4] = 0.0
         self.pack_ref = pack
         # zero shape angles for point sources keep the envelope branch out
         self.cluster_off = pack.cluster_off.to(device=device,
                                                dtype=torch.int32).contiguous()
+        self.record = {k: getattr(self, k) for k in self.FIELDS}
         self.freq0 = None
-        self._flux_cache = {}
-        self._sh_flux_cache = {}
-        self._stack_cache = {}
-        self._sh_stack_cache = {}
+        self._flux_cache = {}    # channel -> ([4, K], [4, S] or None)
+        self._stack_cache = {}   # channels -> ([F, 4, K], [F, 4, S], freqs)
 
     def _flog(self, freq):
         """Log-polynomial spectral exponent per source at `freq`."""
@@ -263,68 +267,62 @@ class GPUPack:
         return torch.where(s0 == 0, torch.zeros_like(s0),
                            torch.sign(s0) * mag)
 
-    def fluxes_at(self, freq, freq0):
-        """Per-source fluxes at channel `freq`; pack fluxes are given at
-        freq0 (sI..) and catalogue f0 (sI0..). Shapelet sources are zero
-        here; their fluxes at the same channel are cached alongside
-        (shapelet_fluxes_at)."""
+    def _channel_fluxes(self, freq, freq0):
+        """(flux [4, K], shapelet flux [4, S] or None) float32 at channel
+        `freq`: within 1 Hz of freq0 the pack fluxes, else the
+        spectral-index scaling of the catalogue fluxes. Remembered per
+        channel."""
         key = round(float(freq), 3)
-        if key in self._flux_cache:
-            return self._flux_cache[key]
-        if abs(freq - freq0) < 1.0:
-            out = (self.sI, self.sQ, self.sU, self.sV)
-            if self.sh is not None:
-                self._sh_flux_cache[key] = self._sh_flux
-        else:
-            flog = self._flog(freq)
-            out = tuple(self._scale(s0, flog) for s0 in
-                        (self.sI0, self.sQ0, self.sU0, self.sV0))
-            if self.sh is not None:
-                self._sh_flux_cache[key] = self._scale(
-                    self._sh_flux0,
-                    flog.index_select(0, self.sh.src)).contiguous()
-        self._flux_cache[key] = out
-        return out
+        hit = self._flux_cache.get(key)
+        if hit is None:
+            if abs(freq - freq0) < 1.0:
+                hit = (self.flux, self._sh_flux)
+            else:
+                flog = self._flog(freq)
+                hit = (self._scale(self.flux0, flog),
+                       None if self.sh is None else self._scale(
+                           self._sh_flux0, flog.index_select(0, self.sh.src)))
+            self._flux_cache[key] = hit
+        return hit
 
-    def flux_stack(self, freqs, freq0):
-        """(fluxes [F, 4, K] float32, freqs [F] float64) on the device for
-        the all-channels kernels: row f stacks fluxes_at(freqs[f], freq0),
-        so a channel within 1 Hz of freq0 carries the pack fluxes and every
-        other one the spectral-index scaling of the catalogue fluxes.
+    def _channel_stacks(self, freqs, freq0):
+        """(flux [F, 4, K], shapelet flux [F, 4, S] or None, freqs [F]
+        float64) on the device: row f is _channel_fluxes(freqs[f], freq0).
         Remembered per frequency tuple."""
         key = (tuple(round(float(f), 3) for f in freqs),
                round(float(freq0), 3))
         hit = self._stack_cache.get(key)
         if hit is None:
-            if len(self._stack_cache) > 16:   # bound long multi-MS runs
-                self._stack_cache.pop(next(iter(self._stack_cache)))
-            flux = torch.stack([torch.stack(self.fluxes_at(float(f), freq0))
-                                for f in freqs]).contiguous()
-            fq = torch.tensor([float(f) for f in freqs], dtype=torch.float64,
-                              device=self.ll.device)
-            hit = self._stack_cache[key] = (flux, fq)
+            rows = [self._channel_fluxes(float(f), freq0) for f in freqs]
+            hit = dispatch.remember(self._stack_cache, key, (
+                torch.stack([r[0] for r in rows]),
+                None if self.sh is None else torch.stack(
+                    [r[1] for r in rows]),
+                torch.tensor([float(f) for f in freqs], dtype=torch.float64,
+                             device=self.ll.device)), 16)
         return hit
+
+    def fluxes_at(self, freq, freq0):
+        """Per-source fluxes (sI, sQ, sU, sV) at channel `freq`, the rows of
+        a [4, K] stack; pack fluxes are given at freq0 and catalogue f0.
+        Shapelet sources are zero here (shapelet_fluxes_at has theirs)."""
+        return tuple(self._channel_fluxes(freq, freq0)[0])
 
     def shapelet_fluxes_at(self, freq, freq0):
         """Un-zeroed I, Q, U, V of the shapelet sources at channel `freq`,
         [4, S] float32 in table order."""
-        self.fluxes_at(freq, freq0)
-        return self._sh_flux_cache[round(float(freq), 3)]
+        return self._channel_fluxes(freq, freq0)[1]
+
+    def flux_stack(self, freqs, freq0):
+        """(fluxes [F, 4, K] float32, freqs [F] float64) on the device for
+        the all-channels kernels: row f stacks fluxes_at(freqs[f], freq0)."""
+        flux, _, fq = self._channel_stacks(freqs, freq0)
+        return flux, fq
 
     def shapelet_flux_stack(self, freqs, freq0):
         """Fluxes [F, 4, S] float32 of the shapelet sources for the
-        all-channels kernels: row f is shapelet_fluxes_at(freqs[f], freq0).
-        Remembered per frequency tuple, like flux_stack."""
-        key = (tuple(round(float(f), 3) for f in freqs),
-               round(float(freq0), 3))
-        hit = self._sh_stack_cache.get(key)
-        if hit is None:
-            if len(self._sh_stack_cache) > 16:   # bound long multi-MS runs
-                self._sh_stack_cache.pop(next(iter(self._sh_stack_cache)))
-            hit = self._sh_stack_cache[key] = torch.stack(
-                [self.shapelet_fluxes_at(float(f), freq0)
-                 for f in freqs]).contiguous()
-        return hit
+        all-channels kernels: row f is shapelet_fluxes_at(freqs[f], freq0)."""
+        return self._channel_stacks(freqs, freq0)[1]
 
     def r1_for(self, dec0):
         """Time-smear source-distance term sqrt(ll^2+(sin(dec0) mm)^2)
@@ -340,9 +338,7 @@ _gpu_pack_cache = {}
 def gpu_pack(pack, device):
     key = (dispatch.obj_token(pack), str(device))
     if key not in _gpu_pack_cache:
-        if len(_gpu_pack_cache) > 16:   # bound long multi-MS runs
-            _gpu_pack_cache.pop(next(iter(_gpu_pack_cache)))
-        _gpu_pack_cache[key] = GPUPack(pack, device)
+        dispatch.remember(_gpu_pack_cache, key, GPUPack(pack, device), 16)
     return _gpu_pack_cache[key]
 
 
@@ -361,44 +357,29 @@ def _pair_range(pairs):
     if hit is None:
         hit = (int(pairs.min()), int(pairs.max()))
         if key is not None:
-            if len(_nsta_memo) > 64:
-                _nsta_memo.pop(next(iter(_nsta_memo)))
-            _nsta_memo[key] = hit
+            dispatch.remember(_nsta_memo, key, hit, 64)
     return hit
 
 
-def _check_ejones(ejones, beam, pairs, Nbase, R, K):
-    """Host-side contract of the E-Jones kernels, which index ejones and
-    beam by timeslot, source and station with no checks of their own.
-    Returns the station count N."""
-    if pairs is None:
-        raise ValueError("ejones needs the station-pair table `pairs`")
-    if ejones.dim() != 5 or tuple(ejones.shape[3:]) != (2, 2):
+def _check_ejones(ejones, beam, pairs, Nbase, R, K, dev):
+    """Host-side contract of the single-channel E-Jones kernels:
+    _check_beam_channels for the one channel of ejones [T, K, NE, 2, 2] and
+    beam [T, K, N], with the station range taken over every row of the
+    caller's `pairs`, whose answer is remembered per tensor. A beam that is
+    not three-dimensional is left for the extension to refuse. Returns the
+    extension's keyword arguments."""
+    if ejones.dim() != 5:
         raise ValueError("ejones must be [T, K, NE, 2, 2], got "
                          f"{tuple(ejones.shape)}")
-    Nbase = int(Nbase) or int(pairs.shape[0])
-    if pairs.dim() != 2 or pairs.shape[0] < Nbase or pairs.shape[1] != 2:
-        raise ValueError("pairs must be [Nbase, 2]")
-    T, Ke, NE = (int(x) for x in ejones.shape[:3])
-    if T * Nbase != R:
-        raise ValueError(f"ejones has {T} timeslots of {Nbase} baselines, "
-                         f"the predict has {R} rows")
-    if Ke < K:
-        raise ValueError(f"ejones covers {Ke} sources, the pack has {K}")
-    lo, hi = _pair_range(pairs)
-    if beam is not None:
-        if tuple(beam.shape[:2]) != (T, Ke):
-            raise ValueError("beam and ejones disagree on [T, K]")
-        N = int(beam.shape[2])
-    else:
-        N = NE if NE != 1 else hi + 1
-    if lo < 0 or hi >= N:
-        raise ValueError(f"pairs name stations {lo}..{hi}, outside the "
-                         f"{N} stations of the beam buffers")
-    if NE not in (1, N):
-        raise ValueError(f"ejones holds {NE} patterns per source; must be "
-                         f"1 or the station count {N}")
-    return N
+    beam3 = beam is not None and beam.dim() == 3
+    kw = _check_beam_channels(beam[None] if beam3 else None, ejones[None],
+                              pairs, Nbase, 1, R, K, dev, all_pairs=True)
+    kw['ejones'] = kw['ejones'][0]
+    if beam3:
+        kw['beam'] = kw['beam'][0]
+    elif beam is not None:
+        kw['beam'] = beam.to(device=dev, dtype=torch.float32).contiguous()
+    return kw
 
 
 def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
@@ -421,61 +402,56 @@ def predict_coh(pack, u, v, w, freq, freq0, fdelta, tdelta, dec0,
     kernels. `pairs` is required with it. The first call with a new pair
     table reads its index range back for the bounds check."""
     gp = pack if isinstance(pack, GPUPack) else gpu_pack(pack, u.device)
-    sI, sQ, sU, sV = gp.fluxes_at(freq, freq0)
+    flux, sh_flux = gp._channel_fluxes(freq, freq0)
     r1 = gp.r1_for(dec0)
-    u64 = u.to(torch.float64).contiguous()
-    v64 = v.to(torch.float64).contiguous()
-    w64 = w.to(torch.float64).contiguous()
-    Nsta = 0
+    uvw = [t.to(torch.float64).contiguous() for t in (u, v, w)]
+    chan = (float(freq), float(fdelta) * 0.5, float(tdelta))
+    bm = {}
     if ejones is not None:
         if os.environ.get('SAGECAL_SHAPELET_HOST') == '1' \
                 and gp.sh is not None:
             raise RuntimeError("the torch shapelet mirror has no E-Jones")
-        Nsta = _check_ejones(ejones, beam, pairs, Nbase, int(u.shape[0]),
-                             gp.K)
-        ejones = ejones.to(device=u.device,
-                           dtype=torch.complex64).contiguous()
-    if beam is not None or ejones is not None:
-        if beam is not None:
-            beam = beam.to(device=u.device,
-                           dtype=torch.float32).contiguous()
+        bm = _check_ejones(ejones, beam, pairs, Nbase, int(u.shape[0]),
+                           gp.K, u.device)
+    elif beam is not None:
         Nbase = int(Nbase) or int(pairs.shape[0])
-        pairs = pairs[:Nbase].to(device=u.device,
-                                 dtype=torch.int32).contiguous()
-    ej = {} if ejones is None else {'ejones': ejones, 'Nsta': Nsta}
-    out = _ext().predict_coh(
-        u64, v64, w64, gp.ll, gp.mm, gp.nn1, sI, sQ, sU, sV,
-        gp.eX, gp.eY, gp.eP, gp.cxi, gp.sxi, gp.cphi, gp.sphi, r1,
-        gp.stype, gp.cluster_off, float(freq), float(fdelta) * 0.5,
-        float(tdelta), beam=beam, pairs=pairs, Nbase=int(Nbase), **ej)
+        bm = dict(
+            beam=beam.to(device=u.device, dtype=torch.float32).contiguous(),
+            pairs=pairs[:Nbase].to(device=u.device,
+                                   dtype=torch.int32).contiguous(),
+            Nbase=Nbase)
+    out = _ext().predict_coh(*uvw, gp.record, flux, r1, *chan, **bm)
     if gp.sh is not None:
         tab = gp.sh
-        flux = gp.shapelet_fluxes_at(freq, freq0)
         r1s = r1.index_select(0, tab.src)
         if beam is not None and beam.shape[1] < tab.K:
             raise ValueError("beam covers fewer sources than the pack")
         if os.environ.get('SAGECAL_SHAPELET_HOST') == '1':
             # torch mirror of the kernel (same table), for cross-checks
-            add = shapelet_coh_torch(tab, flux, r1s, u64, v64, w64,
-                                     float(freq), float(fdelta),
-                                     float(tdelta), beam, pairs, Nbase)
+            add = shapelet_coh_torch(
+                tab, sh_flux, r1s, *uvw, float(freq), float(fdelta),
+                float(tdelta), bm.get('beam'), bm.get('pairs'),
+                bm.get('Nbase', 0))
             out = out + add.reshape(gp.M, -1, 4).to(out.dtype)
         else:
-            _ext().shapelet_coh_add(
-                out, u64, v64, w64, *(getattr(tab, k) for k in tab.FIELDS),
-                flux, r1s, float(freq), float(fdelta) * 0.5, float(tdelta),
-                beam=beam, pairs=pairs, Nbase=int(Nbase), **ej)
+            _ext().shapelet_coh_add(out, *uvw, tab.record, sh_flux, r1s,
+                                    *chan, **bm)
     return out.view(gp.M, -1, 2, 2)
 
 
-def _mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0):
-    """Positional arguments u .. tdelta of the extension's all-channels
-    entry points."""
-    flux, fq = gp.flux_stack(freqs, freq0)
-    f64 = lambda t: t.to(torch.float64).contiguous()
-    return (f64(u), f64(v), f64(w), gp.ll, gp.mm, gp.nn1, flux, gp.eX,
-            gp.eY, gp.eP, gp.cxi, gp.sxi, gp.cphi, gp.sphi, gp.r1_for(dec0),
-            gp.stype, gp.cluster_off, fq, float(fdelta) * 0.5, float(tdelta))
+def _mf_call_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0):
+    """The per-call values of the extension's all-channels entry points, by
+    name: rows (u, v, w), the flux stacks and r1 of the pack (`src`) and of
+    its shapelet table (`tab`, None without one), and chan (freqs, fdelta2,
+    tdelta). Device work only, no synchronisation."""
+    flux, sh_flux, fq = gp._channel_stacks(freqs, freq0)
+    r1 = gp.r1_for(dec0)
+    return dict(
+        rows=[t.to(torch.float64).contiguous() for t in (u, v, w)],
+        src=(flux, r1),
+        tab=None if gp.sh is None else (sh_flux,
+                                        r1.index_select(0, gp.sh.src)),
+        chan=(fq, float(fdelta) * 0.5, float(tdelta)))
 
 
 def _mf_pack(pack, device, what, shapelets=False):
@@ -487,32 +463,20 @@ def _mf_pack(pack, device, what, shapelets=False):
     return gp
 
 
-def _shapelet_mf_args(gp, src_args, freqs, freq0):
-    """Positional arguments u .. tdelta of the extension's all-channels
-    shapelet entry points, from those of the main call (_mf_source_args):
-    the same rows, r1, frequencies and widths, the pack's mode table and
-    the shapelet flux stack. Device work only, no synchronisation."""
-    tab = gp.sh
-    u, v, w = src_args[:3]
-    r1, fq, fdelta2, tdelta = src_args[14], *src_args[17:]
-    return (u, v, w, *(getattr(tab, k) for k in tab.FIELDS), tab.entry_off,
-            gp.shapelet_flux_stack(freqs, freq0),
-            r1.index_select(0, tab.src), fq, fdelta2, tdelta)
-
-
 def _check_beam_channels(beam, ejones, pairs, Nbase, F, R, K, dev,
-                         negative_ok=False, Nsta=None):
+                         negative_ok=False, Nsta=None, all_pairs=False):
     """Host-side contract of the beamed all-channels kernels, which index
     beam [F, T, Ke, N] and ejones [F, T, Ke, NE, 2, 2] (or [F, T, Ke, 2, 2],
     one pattern, NE = 1) by channel, timeslot, source and station with no
-    checks of their own. Checked once here, as _check_ejones does for one
-    channel: leading dimension F, [T, Ke] agreement, Ke >= K, the station
-    range of `pairs` inside N, NE in (1, N). negative_ok: the residual
-    kernels keep x on a row with a negative pair entry and look nothing up
-    for it, the predict kernels have no such row. Nsta: the station count
-    when the caller has one (J's), else beam's, else NE or the largest pair
-    entry + 1. Returns the keyword arguments of the extension: beam
-    float32, ejones complex64 six-dimensional, pairs int32 [Nbase, 2], all
+    checks of their own. Checked once here, and through _check_ejones for
+    the single-channel kernels: leading dimension F, [T, Ke] agreement,
+    Ke >= K, the station range of `pairs` inside N, NE in (1, N).
+    negative_ok: the residual kernels keep x on a row with a negative pair
+    entry and look nothing up for it, the predict kernels have no such row.
+    Nsta: the station count when the caller has one (J's), else beam's, else
+    NE or the largest pair entry + 1. all_pairs: the station range of every
+    row of `pairs`, not of the first Nbase alone. Returns the keyword
+    arguments of the extension: beam float32, ejones complex64 six-dimensional, pairs int32 [Nbase, 2], all
     contiguous on `dev`, Nbase and Nsta."""
     if pairs is None:
         raise ValueError("beam and ejones need the station-pair table "
@@ -527,7 +491,7 @@ def _check_beam_channels(beam, ejones, pairs, Nbase, F, R, K, dev,
     T = R // Nbase
     # the range is remembered per tensor object: ask for the caller's own
     # table where all of it is read
-    lo, hi = _pair_range(pairs if pairs.shape[0] == Nbase
+    lo, hi = _pair_range(pairs if all_pairs or pairs.shape[0] == Nbase
                          else pairs[:Nbase])
     pairs = pairs[:Nbase].to(device=dev, dtype=torch.int32).contiguous()
     N = Nsta
@@ -620,11 +584,12 @@ def predict_coh_channels(pack, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
     if beam is not None or ejones is not None:
         bm = _check_beam_channels(beam, ejones, pairs, Nbase, F, R, gp.K,
                                   u.device)
-    args = _mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0)
-    out = _ext().predict_coh_channels(*args, mean=reduce == 'mean', **bm)
+    a = _mf_call_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0)
+    out = _ext().predict_coh_channels(*a['rows'], gp.record, *a['src'],
+                                      *a['chan'], mean=reduce == 'mean', **bm)
     if gp.sh is not None:
         _ext().shapelet_coh_channels_add(
-            out, *_shapelet_mf_args(gp, args, freqs, freq0),
+            out, *a['rows'], gp.sh.record, *a['tab'], *a['chan'],
             mean=reduce == 'mean', K=gp.K, **bm)
     return out.view(*out.shape[:-1], 2, 2)
 
@@ -689,15 +654,15 @@ def residuals_multifreq(pack, x, u, v, w, freqs, freq0, fdelta, tdelta, dec0,
         bm = _check_beam_channels(beam, ejones, pairs, 0, F, R, gp.K, dev,
                                   negative_ok=True, Nsta=N)
         bm = {k: bm[k] for k in ('beam', 'ejones', 'Nsta') if k in bm}
-    args = _mf_source_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0)
+    a = _mf_call_args(gp, u, v, w, freqs, freq0, fdelta, tdelta, dec0)
     J4 = J.to(torch.complex64).reshape(Mt, N, 4).contiguous()
     out = _ext().residuals_multifreq(
-        x.to(torch.complex64).reshape(F, R, 4).contiguous(), *args, J4,
-        chunk_tab, pairs, skip, **bm)
+        x.to(torch.complex64).reshape(F, R, 4).contiguous(), *a['rows'],
+        gp.record, *a['src'], *a['chan'], J4, chunk_tab, pairs, skip, **bm)
     if gp.sh is not None:
         _ext().shapelet_residuals_add(
-            out, *_shapelet_mf_args(gp, args, freqs, freq0), J4, chunk_tab,
-            pairs, skip, K=gp.K, **bm)
+            out, *a['rows'], gp.sh.record, *a['tab'], *a['chan'], J4,
+            chunk_tab, pairs, skip, K=gp.K, **bm)
     return out.view(F, R, 2, 2)
 
 
@@ -705,7 +670,6 @@ def _beam_geometry_args(elem, nelem, du, below):
     """Checks the arguments array_beam_gains and station_beam_gains share
     and returns them as the extension wants them: (elem float64, nelem
     int32, du float64, below uint8), contiguous on elem's device."""
-    import numpy as np
     if not torch.is_tensor(elem) or not elem.is_cuda:
         raise ValueError("elem must be a device tensor [N, Emax, 3]")
     if elem.dim() != 3 or elem.shape[2] != 3 or elem.shape[1] < 1:
@@ -755,7 +719,6 @@ def station_beam_gains(elem, nelem, du, below, freqs, tile=None,
     a tile, 1 <= D <= 64, on elem's device; du_tile [T, K, 3] source minus
     tile pointing direction. Returns [F, T, K, N] float32; row f is
     the `beam` argument of predict_coh at freqs[f]."""
-    import numpy as np
     from ..constants import C_LIGHT
     elem, ne, du, below = _beam_geometry_args(elem, nelem, du, below)
     dev, N = elem.device, int(elem.shape[0])
@@ -793,7 +756,6 @@ def element_jones(coeffs, az, el, freqs, device=None):
     dipole, all four entries exactly zero where el < 0 (compared in fp64).
     `device`: where to evaluate; by default the device of az if that is a
     device tensor, else the current one."""
-    import numpy as np
     ext = _ext()
     M = int(coeffs.M)
     if not 1 <= M <= ext.ELEMENT_BEAM_MAX_M:   # the kernel's unroll cap
@@ -859,9 +821,7 @@ class BaselineLayout:
                                   dtype=torch.int32).contiguous()
             hit = (pairs, self._pidx_for(pairs, Nbase, N, device))
             if mkey is not None:
-                if len(_layout_memo) > 64:   # bound long multi-MS runs
-                    _layout_memo.pop(next(iter(_layout_memo)))
-                _layout_memo[mkey] = hit
+                dispatch.remember(_layout_memo, mkey, hit, 64)
         self.pairs, self.pidx = hit
 
     @staticmethod
@@ -998,9 +958,7 @@ def _table_memo(kind, table, extra, build):
         return build()
     hit = _lbfgs_tab_memo.get(key)
     if hit is None:
-        if len(_lbfgs_tab_memo) > 64:
-            _lbfgs_tab_memo.pop(next(iter(_lbfgs_tab_memo)))
-        hit = _lbfgs_tab_memo[key] = build()
+        hit = dispatch.remember(_lbfgs_tab_memo, key, build(), 64)
     return hit
 
 
@@ -1291,10 +1249,9 @@ def chol_solve_damped(JtJ, Jtr, mu):
     sc = _chol_scratch.get(key)
     want = (JtJ.shape[0], 2 * JtJ.shape[1] * JtJ.shape[2])
     if sc is None or tuple(sc.shape) != want:
-        if len(_chol_scratch) > 8:   # bound long multi-config runs
-            _chol_scratch.pop(next(iter(_chol_scratch)))
-        sc = torch.empty(want, dtype=JtJ.dtype, device=JtJ.device)
-        _chol_scratch[key] = sc
+        sc = dispatch.remember(
+            _chol_scratch, key,
+            torch.empty(want, dtype=JtJ.dtype, device=JtJ.device), 8)
     # n >= 384: multi-workgroup right-looking path — the trailing-update
     # SYRK tiles spread over the whole chip instead of 1 WG/problem
     # (65% of step time at [5,512,512]; see profiles/). Small n stays on

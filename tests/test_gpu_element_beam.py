@@ -257,6 +257,22 @@ def test_argument_checks(sky):
         _gpu_predict(sky, ejones=sky['ej'], Nbase=sky['Nbase'])
     with pytest.raises(ValueError):           # fewer sources than the pack
         _gpu_predict(sky, ejones=sky['ej'][:, :K - 1].contiguous(), **kw)
+    # the whole pair table of the tile, as beams.predict_coh_withbeam gives
+    # it: its range is read back once and remembered for the tensor
+    bb = sky['bb'].to(device=DEV, dtype=torch.int32)
+    assert bb.shape[0] == T * sky['Nbase']
+    long = dict(pairs=bb, Nbase=sky['Nbase'])
+    first = _gpu_predict(sky, ejones=sky['ej'], **long)
+    memo = dict(hip_host._nsta_memo)
+    assert torch.equal(first, _gpu_predict(sky, ejones=sky['ej'], **long))
+    assert hip_host._nsta_memo == memo
+    assert torch.equal(first, _gpu_predict(sky, ejones=sky['ej'], **kw))
+    bad = bb.clone()
+    bad[-1, 1] = N                            # a station beyond Nbase rows
+    with pytest.raises(ValueError):
+        _gpu_predict(sky, ejones=sky['ej'], pairs=bad, Nbase=sky['Nbase'])
+    with pytest.raises(RuntimeError):         # a beam that is not [T, K, N]
+        _gpu_predict(sky, ejones=sky['ej'], beam=sky['beam'][..., None], **kw)
     elem = torch.zeros(2, 4, 3, dtype=torch.float64, device=DEV)
     du = torch.zeros(T, K, 3, dtype=torch.float64)
     below = torch.zeros(T, K, dtype=torch.uint8)
@@ -281,15 +297,13 @@ def test_extension_rejects_malformed_beam(sky):
     pairs = torch.tensor([[0, 1], [0, 2], [1, 2]], dtype=torch.int32,
                          device=dev)
     beam = torch.full((1, 2, 3), 0.5, dtype=torch.float32, device=dev)
-    sI, sQ, sU, sV = gp.fluxes_at(S.FREQ0, S.FREQ0)
+    flux4 = torch.stack(gp.fluxes_at(S.FREQ0, S.FREQ0))         # [4, K]
     r1 = gp.r1_for(S.DEC0)
     chan = (S.FREQ0, S.FDELTA * 0.5, S.TDELTA)
 
     def predict(beam, pairs):
-        return ext.predict_coh(
-            u, v, w, gp.ll, gp.mm, gp.nn1, sI, sQ, sU, sV, gp.eX, gp.eY,
-            gp.eP, gp.cxi, gp.sxi, gp.cphi, gp.sphi, r1, gp.stype,
-            gp.cluster_off, *chan, beam=beam, pairs=pairs, Nbase=Nbase)
+        return ext.predict_coh(u, v, w, gp.record, flux4, r1, *chan,
+                               beam=beam, pairs=pairs, Nbase=Nbase)
 
     sgp = hip_host.gpu_pack(sky['pack'], dev)
     tab = sgp.sh
@@ -298,9 +312,8 @@ def test_extension_rejects_malformed_beam(sky):
     out = torch.zeros(sgp.M, 3, 4, dtype=torch.complex64, device=dev)
 
     def shapelet_add(beam, pairs):
-        ext.shapelet_coh_add(
-            out, u, v, w, *(getattr(tab, k) for k in tab.FIELDS), flux, r1s,
-            *chan, beam=beam, pairs=pairs, Nbase=Nbase)
+        ext.shapelet_coh_add(out, u, v, w, tab.record, flux, r1s, *chan,
+                             beam=beam, pairs=pairs, Nbase=Nbase)
 
     assert predict(beam, pairs).shape == (2, 3, 4)    # the inputs are sound
     bad = {'float64 beam': (beam.double(), pairs),

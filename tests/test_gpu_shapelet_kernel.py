@@ -133,11 +133,10 @@ def test_no_shapelets_is_the_plain_kernel(sky):
     u, v, w = sky['uvw_d']
     got = hip_host.predict_coh(pack, u, v, w, S.FREQ0, S.FREQ0, S.FDELTA,
                                S.TDELTA, S.DEC0)
-    sI, sQ, sU, sV = gp.fluxes_at(S.FREQ0, S.FREQ0)
+    flux = torch.stack(gp.fluxes_at(S.FREQ0, S.FREQ0))          # [4, K]
     direct = hip_host._ext().predict_coh(
-        u, v, w, gp.ll, gp.mm, gp.nn1, sI, sQ, sU, sV, gp.eX, gp.eY, gp.eP,
-        gp.cxi, gp.sxi, gp.cphi, gp.sphi, gp.r1_for(S.DEC0), gp.stype,
-        gp.cluster_off, S.FREQ0, S.FDELTA * 0.5, S.TDELTA)
+        u, v, w, gp.record, flux, gp.r1_for(S.DEC0), S.FREQ0,
+        S.FDELTA * 0.5, S.TDELTA)
     assert torch.equal(got, direct.view(pack.M, -1, 2, 2))
 
 
