@@ -344,6 +344,15 @@ def rtr_kernel_on():
             and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
 
 
+def chol_blocked_on():
+    """SAGECAL_CHOL_BLOCKED=1 opts hip_host.chol_solve_damped, and with it
+    lm.joint_lm_solve, into the blocked kernels of cholesky_blocked.hip for
+    n > 4096 (up to 16384); off by default, and SAGECAL_FORCE_REFERENCE=1
+    overrides it."""
+    return (os.environ.get('SAGECAL_CHOL_BLOCKED') == '1'
+            and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
+
+
 def rtr_tcg(JtJ, Jtr, J, iw, delta, maxit=12, kappa=0.01):
     """The inner solve of one RTR outer iteration at J [n, N, 2, 2], from
     the normal equations JtJ [n, 8N, 8N], Jtr [n, 8N] in reference.vecR

@@ -770,6 +770,12 @@ std::vector<torch::Tensor> chol_solve_mw(
   return chol_solve_with(launch_chol_mw, JtJ, Jtr, mu, scratch);
 }
 
+std::vector<torch::Tensor> chol_solve_blocked(
+    torch::Tensor JtJ, torch::Tensor Jtr, torch::Tensor mu,
+    torch::Tensor scratch) {
+  return chol_solve_with(launch_chol_blocked, JtJ, Jtr, mu, scratch);
+}
+
 std::vector<torch::Tensor> jtr_grad(
     torch::Tensor x, torch::Tensor coh, torch::Tensor J,
     torch::Tensor pairs, torch::Tensor chunk_tab, torch::Tensor pidx,
@@ -1001,6 +1007,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("chol_solve", &chol_solve, "batched damped Cholesky solve (gfx950)");
   m.def("chol_solve_mw", &chol_solve_mw,
         "multi-workgroup damped Cholesky solve (gfx950)");
+  m.def("chol_solve_blocked", &chol_solve_blocked,
+        "blocked damped Cholesky solve, 32 <= n <= 16384 (gfx950)");
   // The predict entry points take the per-source arrays as the record `src`
   // (hip_host.GPUPack.record) or the shapelet mode table as the record
   // `tab` (hip_host.ShapeletTable.record), dicts from field name to tensor.

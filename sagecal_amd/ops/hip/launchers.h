@@ -302,13 +302,17 @@ hipError_t launch_apply_jones(
     const int* chunk_tab, int Nbase, int T, int N, int nseg, int M, int sub,
     float2* out, hipStream_t stream);
 
-// dp = (JtJ + mu I)^-1 Jtr, one workgroup per problem (chol_solve) or the
-// multi-workgroup kernel sequence (chol_mw); same contract, n a multiple of
-// the block size, Lbuf 2*n*n floats per problem
+// dp = (JtJ + mu I)^-1 Jtr, one workgroup per problem (chol_solve), the
+// multi-workgroup kernel sequence (chol_mw) or the blocked sequence for
+// n up to 16384 (chol_blocked); same contract, n a multiple of the block
+// size, Lbuf 2*n*n floats per problem
 hipError_t launch_chol_solve(
     const float* JtJ, const float* Jtr, const float* mu, int n, int batch,
     float* Lbuf, float* dp, int* info, hipStream_t stream);
 hipError_t launch_chol_mw(
+    const float* JtJ, const float* Jtr, const float* mu, int n, int batch,
+    float* Lbuf, float* dp, int* info, hipStream_t stream);
+hipError_t launch_chol_blocked(
     const float* JtJ, const float* Jtr, const float* mu, int n, int batch,
     float* Lbuf, float* dp, int* info, hipStream_t stream);
 

@@ -10,6 +10,7 @@
 #include "joint_jtj.hip"
 #include "rtr_tcg.hip"
 #include "cholesky.hip"
+#include "cholesky_blocked.hip"
 #include "element_beam.hip"
 
 // One thread per row in blocks of 128: the plain kernel, or with
@@ -383,6 +384,36 @@ hipError_t launch_chol_mw(
       hipLaunchKernelGGL(k_cholmw_syrk, dim3(batch * ntiles), dim3(64), 0,
           stream, n, k, ntiles, Lbuf);
     }
+  }
+  hipLaunchKernelGGL(k_cholmw_subst, dim3(batch), dim3(NTH), 0, stream,
+      n, Lbuf, dp, info);
+  return hipGetLastError();
+}
+
+// blocked variant for large n: outer blocks of XB columns, three launches
+// per block (see cholesky_blocked.hip); init and the backward pass are the
+// mw kernels
+hipError_t launch_chol_blocked(
+    const float* JtJ, const float* Jtr, const float* mu, int n, int batch,
+    float* Lbuf, float* dp, int* info, hipStream_t stream) {
+  if (!chol_shape_ok(n, batch, MAXN_CHOL_XL)) return hipErrorInvalidValue;
+  const long long tmax = (n + XB - 1) / XB;
+  if (batch * (tmax * (tmax + 1) / 2) > 0x7fffffffLL)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cholmw_init, dim3(batch, INIT_SLICES), dim3(NTH), 0,
+      stream, JtJ, Jtr, mu, n, Lbuf, dp);
+  for (int k = 0; k < n; k += XB) {
+    hipLaunchKernelGGL(k_cholxl_diag, dim3(batch), dim3(NTH),
+        cholxl_diag_lds_bytes(), stream, n, k, Lbuf, dp, info);
+    const int rest = n - k - XB;          // rows below the block
+    if (rest <= 0) break;
+    const int nstrips = (rest + XS - 1) / XS;
+    hipLaunchKernelGGL(k_cholxl_trsm, dim3(batch * nstrips), dim3(NTH),
+        cholxl_trsm_lds_bytes(), stream, n, k, nstrips, Lbuf, dp);
+    const int tcnt = (rest + XB - 1) / XB;
+    const int ntiles = tcnt * (tcnt + 1) / 2;
+    hipLaunchKernelGGL(k_cholxl_syrk, dim3(batch * ntiles), dim3(XTH), 0,
+        stream, n, k, ntiles, Lbuf);
   }
   hipLaunchKernelGGL(k_cholmw_subst, dim3(batch), dim3(NTH), 0, stream,
       n, Lbuf, dp, info);

@@ -1258,7 +1258,13 @@ def chol_solve_damped(JtJ, Jtr, mu):
     # the single fused kernel (lower launch count wins).
     mw = os.environ.get('SAGECAL_CHOL_MW')
     use_mw = (JtJ.shape[1] >= 384) if mw is None else mw == '1'
-    if use_mw:
+    if JtJ.shape[1] > 4096 and dispatch.chol_blocked_on():
+        # above the mw limit: outer blocks of 128 with LDS-tiled rank-128
+        # trailing updates (cholesky_blocked.hip), n <= 16384
+        dp, info = _ext().chol_solve_blocked(
+            JtJ.contiguous(), Jtr.contiguous(),
+            mu.to(torch.float32).contiguous(), sc)
+    elif use_mw:
         # chunked panels (round 2) support up to n=4096
         assert JtJ.shape[1] <= 4096, "mw Cholesky supports n <= 4096"
         dp, info = _ext().chol_solve_mw(JtJ.contiguous(), Jtr.contiguous(),

@@ -270,7 +270,9 @@ def joint_lm_solve(x, cohs, J_packed, chunk_off, nchunks, bb, T, Nbase,
     SAGECAL_JOINT_KERNEL=1 on device tensors: the normal equations and the
     trial cost come from the kernels of joint_jtj.hip (ops.joint_jtj_jtr,
     ops.joint_cost), and with the same chunk count K > 1 in every cluster
-    the K uncoupled blocks run as one batched LM (_joint_lm_blocked)."""
+    the K uncoupled blocks run as one batched LM (_joint_lm_blocked). With
+    SAGECAL_CHOL_BLOCKED=1 as well, systems above 4096 unknowns (up to
+    16384) are solved by the blocked Cholesky kernels instead of torch."""
     from ..ops import reference as R
     J = J_packed.clone()
     dev = x.device
@@ -313,23 +315,40 @@ def joint_lm_solve(x, cohs, J_packed, chunk_off, nchunks, bb, T, Nbase,
 
     H, g, cost = assemble(J)
     cost = float(cost)
-    eye = torch.eye(P, dtype=rdt, device=dev)
+    # SAGECAL_CHOL_BLOCKED=1: above the mw kernels' limit the damped solve
+    # runs in the blocked Cholesky kernels, on H as it is
+    hip_chol = kernels and ops.chol_blocked_on() and 4096 < P <= 16384
+    if hip_chol:
+        from ..ops.hip_host import chol_solve_damped
+    else:
+        eye = torch.eye(P, dtype=rdt, device=dev)
     for it in range(maxiter):
         if mu is None:
             mu = tau * float(H.diagonal().max())
         if float(g.abs().max()) < eps1:
             break
-        A = H + mu * eye
-        try:
-            L = torch.linalg.cholesky(A)
-            dp = torch.cholesky_solve(g.unsqueeze(-1), L).squeeze(-1)
-        except Exception:
-            dp = torch.linalg.lstsq(A, g.unsqueeze(-1)).solution.squeeze(-1)
-        Jn = J + torch.view_as_complex(
-            dp.reshape(Mt, N, 2, 2, 2).contiguous())
-        cn = cost_of(Jn)
-        denom = float((dp * (mu * dp + g)).sum())
-        rho = (cost - cn) / max(denom, 1e-300)
+        failed = False
+        if hip_chol:
+            dp = chol_solve_damped(
+                H[None], g[None],
+                torch.tensor([mu], dtype=torch.float32, device=dev))[0]
+            failed = bool(torch.isnan(dp).any())
+        else:
+            A = H + mu * eye
+            try:
+                L = torch.linalg.cholesky(A)
+                dp = torch.cholesky_solve(g.unsqueeze(-1), L).squeeze(-1)
+            except Exception:
+                dp = torch.linalg.lstsq(
+                    A, g.unsqueeze(-1)).solution.squeeze(-1)
+        if failed:              # a NaN row: the factorisation broke down
+            rho = -1.0
+        else:
+            Jn = J + torch.view_as_complex(
+                dp.reshape(Mt, N, 2, 2, 2).contiguous())
+            cn = cost_of(Jn)
+            denom = float((dp * (mu * dp + g)).sum())
+            rho = (cost - cn) / max(denom, 1e-300)
         if rho > 0:
             J = Jn
             cost = cn
@@ -373,7 +392,9 @@ def _joint_lm_blocked(x, cohs, J, chunk_off, nchunks, bb, T, Nbase, maxiter,
     mu = tau * H.diagonal(dim1=-2, dim2=-1).max(dim=-1).values
     nu = torch.full_like(mu, 2.0)
     for it in range(maxiter):
-        if Pb <= 4096:                      # the Cholesky kernels' limit
+        # the Cholesky kernels' limit: 4096, or with SAGECAL_CHOL_BLOCKED=1
+        # the 16384 of the blocked kernels
+        if Pb <= 4096 or (ops.chol_blocked_on() and Pb <= 16384):
             dp = chol_solve_damped(H, g, mu)
         else:
             # H is rebuilt before its next use. One block at a time, the
