@@ -377,6 +377,60 @@ def rtr_tcg(JtJ, Jtr, J, iw, delta, maxit=12, kappa=0.01):
     return g, eta, Heta, stats
 
 
+def leverage_rows(cohs, J, Hinv, chunk_tab, pairs, weights=None):
+    """Leverage lev [M, R] float64 of every visibility row in every
+    cluster's solve: with (p, q) = pairs[b], c = chunk_tab[ci, t] and row
+    r = t*Nbase + b, G1 = C J_q^H, K = J_p C, D1 = diagnostics._lin_blocks(G1)
+    and D2 = diagnostics._anti_blocks(K),
+      lev[ci, r] = tr(D1 Hpp D1^T) + tr(D2 Hqq D2^T) + 2 tr(D1 Hpq D2^T)
+    with Hxy the 8x8 block of Hinv[c] at stations (x, y), times weights[r]
+    when given. cohs [M, R, 2, 2], J [Mt, N, 2, 2], Hinv [Mt, 8N, 8N],
+    chunk_tab [M, T] global chunk ids, pairs [Nbase, 2], R = T * Nbase; a row
+    whose pair has a negative entry gets 0. On the GPU one launch of
+    k_leverage (leverage.hip) in float64 on complex64 inputs; elsewhere this
+    formula in torch on complex128 upcasts, cluster by cluster, with the
+    blocks of Hinv taken per (chunk, pair)."""
+    if _use_hip(cohs):
+        from . import hip_host
+        return hip_host.leverage_rows(cohs, J, Hinv, chunk_tab, pairs,
+                                      weights)
+    from ..solvers import diagnostics as diag
+    M, Rn = int(cohs.shape[0]), int(cohs.shape[1])
+    T, Nbase = int(chunk_tab.shape[1]), int(pairs.shape[0])
+    Mt, N = int(J.shape[0]), int(J.shape[1])
+    if tuple(cohs.shape) != (M, Rn, 2, 2) or chunk_tab.shape[0] != M \
+            or T * Nbase != Rn or tuple(Hinv.shape) != (Mt, 8 * N, 8 * N):
+        raise ValueError("cohs [M, R, 2, 2], Hinv [Mt, 8N, 8N], chunk_tab "
+                         "[M, T] and pairs [Nbase, 2] with T * Nbase rows")
+    dev = cohs.device
+    pr = pairs.to(device=dev, dtype=torch.long)
+    live = (pr >= 0).all(dim=1)
+    p, q = pr.clamp_min(0).unbind(1)
+    Jd = J.to(torch.complex128)
+    H5 = Hinv.to(torch.float64).reshape(Mt, N, 8, N, 8)
+    lev = torch.zeros(M, T, Nbase, dtype=torch.float64, device=dev)
+    for ci in range(M):
+        ct = chunk_tab[ci].to(device=dev, dtype=torch.long)
+        cs, slot = torch.unique(ct, return_inverse=True)
+        c2 = cs[:, None]
+        # [chunks of ci, Nbase, 8, 8], then per timeslot
+        Hpp, Hqq, Hpq = (H5[c2, a[None], :, b[None], :][slot]
+                         for a, b in ((p, p), (q, q), (p, q)))
+        C = cohs[ci].to(torch.complex128).reshape(T, Nbase, 2, 2)
+        G1 = C @ Jd[ct][:, q].conj().transpose(-1, -2)
+        K = Jd[ct][:, p] @ C
+        D1 = diag._lin_blocks(G1.reshape(-1, 2, 2)).reshape(T, Nbase, 8, 8)
+        D2 = diag._anti_blocks(K.reshape(-1, 2, 2)).reshape(T, Nbase, 8, 8)
+        D1t, D2t = D1.transpose(-1, -2), D2.transpose(-1, -2)
+        lev[ci] = (D1 @ Hpp @ D1t + D2 @ Hqq @ D2t
+                   + 2 * (D1 @ Hpq @ D2t)).diagonal(dim1=-2, dim2=-1).sum(-1)
+    lev = torch.where(live[None, None, :], lev, lev.new_zeros(()))
+    lev = lev.reshape(M, Rn)
+    if weights is not None:
+        lev = lev * weights.to(device=dev, dtype=torch.float64)
+    return lev
+
+
 def _joint_blocks(chunk_off, nchunks, blocked):
     """Chunks per cluster Kb of the blocked layout, or None for dense."""
     if not blocked:

@@ -986,8 +986,53 @@ std::vector<torch::Tensor> rtr_tcg(
   return {g, eta, Heta, stats};
 }
 
+// The influence-map leverage of every cluster (leverage.hip): cohs [M, R, 4]
+// and J [Mt, N, 4] complex64, Hinv [Mt, 8N, 8N] float64, optional wts [R]
+// float64, chunk_tab [M, T] and pairs [Nbase, 2] int32 with R == T * Nbase,
+// pieces [E, 4] int32 (ci, c, t0, t1) from hip_host._lbfgs_extents. Returns
+// lev [M, R] float64. The caller guarantees chunk ids below Mt, pair entries
+// below N and pieces that cover chunk_tab.
+torch::Tensor leverage_rows(
+    torch::Tensor cohs, torch::Tensor J, torch::Tensor Hinv,
+    c10::optional<torch::Tensor> wts, torch::Tensor chunk_tab,
+    torch::Tensor pairs, torch::Tensor pieces) {
+  const torch::Device dev = cohs.device();
+  TORCH_CHECK(on_dev(cohs, dev, torch::kComplexFloat) && cohs.dim() == 3 &&
+              cohs.size(0) >= 1 && cohs.size(1) >= 1 && cohs.size(2) == 4,
+              "cohs must be contiguous [M, R, 4] complex64 on the device");
+  const int64_t M = cohs.size(0), R = cohs.size(1);
+  check_solution_tables(J, chunk_tab, pairs, M, R, dev);
+  const int64_t Mt = J.size(0), N = J.size(1);
+  TORCH_CHECK(on_dev(Hinv, dev, torch::kDouble) && Hinv.dim() == 3 &&
+              Hinv.size(0) == Mt && Hinv.size(1) == 8 * N &&
+              Hinv.size(2) == 8 * N,
+              "Hinv must be contiguous [Mt, 8N, 8N] float64 for the Mt chunks "
+              "of J");
+  TORCH_CHECK(!wts.has_value() || on_dev(*wts, dev, torch::kDouble, R),
+              "weights must be contiguous [R] float64");
+  TORCH_CHECK(on_dev(pieces, dev, torch::kInt) && pieces.dim() == 2 &&
+              pieces.size(0) >= 1 && pieces.size(0) <= 65535 &&
+              pieces.size(1) == 4,
+              "pieces must be contiguous [E, 4] int32, E <= 65535");
+  TORCH_CHECK(Mt * N < (int64_t(1) << 27), "too many parameters");
+  check_aligned16({&cohs, &J, &pieces}, "cohs, J and pieces");
+  LeverageArgs a = {};
+  a.cohs = ccptr(cohs); a.J = ccptr(J); a.Hinv = dp(Hinv);
+  a.wts = wts.has_value() ? dp(*wts) : nullptr;
+  a.pairs = ip(pairs); a.pieces = ip(pieces);
+  a.M = (int)M; a.T = (int)chunk_tab.size(1); a.Nbase = (int)pairs.size(0);
+  a.N = (int)N; a.Mt = (int)Mt; a.E = (int)pieces.size(0);
+  auto lev = torch::empty({M, R}, torch::dtype(torch::kDouble).device(dev));
+  CHECK_HIP(launch_leverage(a, lev.data_ptr<double>(), cur_stream()));
+  return lev;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("jtr_grad", &jtr_grad, "gradient-only accumulation (gfx950)");
+  m.def("leverage_rows", &leverage_rows,
+        "influence-map leverage, all clusters in one launch (gfx950)",
+        py::arg("cohs"), py::arg("J"), py::arg("Hinv"), py::arg("wts"),
+        py::arg("chunk_tab"), py::arg("pairs"), py::arg("pieces"));
   m.def("rtr_tcg", &rtr_tcg, "RTR truncated-CG inner solve (gfx950)",
         py::arg("JtJ"), py::arg("Jtr"), py::arg("J"), py::arg("iw"),
         py::arg("delta"), py::arg("maxit"), py::arg("kappa"));

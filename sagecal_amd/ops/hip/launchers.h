@@ -166,7 +166,29 @@ struct RtrTcgArgs {
   float kappa;
 };
 
+// The influence-map leverage (leverage.hip). Rows r = t*Nbase + b,
+// R = T*Nbase. The host guarantees pair entries below N (negative: the row
+// gets 0), chunk ids in 0..Mt-1 and pieces as hip_host._lbfgs_extents
+// builds them from chunk_tab [M, T].
+struct LeverageArgs {
+  const float2* cohs;       // [M, R, 4] coherencies
+  const float2* J;          // [Mt, N, 4] packed solutions
+  const double* Hinv;       // [Mt, 8N, 8N] inverse of the damped JtJ
+  const double* wts;        // [R] row weights, or null
+  const int* pairs;         // [Nbase, 2]
+  const int* pieces;        // [E, 4] (ci, c, t0, t1): timeslots t0 <= t < t1
+                            // of cluster ci, all of global chunk c
+  int M, T, Nbase, N, Mt, E;
+};
+
 extern "C" {
+
+// Threads per workgroup of k_leverage; a workgroup serves WAVE pairs.
+#define LEVERAGE_TB 256
+// lev [M, R] float64, fully written when the pieces cover every (cluster,
+// timeslot). hipErrorInvalidValue: a dimension < 1, a null table, E > 65535
+// or R * M beyond 2^40.
+hipError_t launch_leverage(LeverageArgs a, double* lev, hipStream_t stream);
 
 // Threads per workgroup of k_rtr_tcg and the most parameters of a chunk:
 // a thread owns one float4 of every vector.

@@ -9,6 +9,7 @@
 #include "lbfgs_mf.hip"
 #include "joint_jtj.hip"
 #include "rtr_tcg.hip"
+#include "leverage.hip"
 #include "cholesky.hip"
 #include "cholesky_blocked.hip"
 #include "element_beam.hip"
@@ -301,6 +302,18 @@ hipError_t launch_rtr_tcg(RtrTcgArgs a, float2* g, float2* eta, float2* Heta,
   const size_t lds = (size_t)(2 * 8 * a.N + a.N) * sizeof(float);
   hipLaunchKernelGGL(k_rtr_tcg, dim3(a.n), dim3(RTR_TCG_TB), lds, stream, a,
                      g, eta, Heta, stats);
+  return hipGetLastError();
+}
+
+// one workgroup per (tile of WAVE pairs, piece); static LDS (leverage.hip)
+hipError_t launch_leverage(LeverageArgs a, double* lev, hipStream_t stream) {
+  if (a.M < 1 || a.T < 1 || a.Nbase < 1 || a.N < 1 || a.Mt < 1 || a.E < 1 ||
+      a.E > 65535 || a.cohs == nullptr || a.J == nullptr ||
+      a.Hinv == nullptr || a.pairs == nullptr || a.pieces == nullptr ||
+      lev == nullptr || (long long)a.T * a.Nbase * a.M > (1LL << 40))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_leverage, dim3((a.Nbase + WAVE - 1) / WAVE, a.E),
+                     dim3(LEVERAGE_TB), 0, stream, a, lev);
   return hipGetLastError();
 }
 

@@ -962,11 +962,11 @@ def _table_memo(kind, table, extra, build):
     return hit
 
 
-def _lbfgs_extents(chunk_tab, Mt):
+def _lbfgs_extents(chunk_tab, Mt, tsplit=LBFGS_TSPLIT):
     """(ext [E, 4], ext_off [Mt + 1]) int32 on chunk_tab's device, the walk
-    plan of k_lbfgs_mf_grad: every cluster's row of chunk_tab [M, T] cut
-    into runs of one chunk id, runs longer than LBFGS_TSPLIT cut into pieces
-    of at most that; one extent (ci, c, t0, t1) per piece, sorted by chunk c
+    plan of k_lbfgs_mf_grad and k_leverage: every cluster's row of chunk_tab
+    [M, T] cut into runs of one chunk id, runs longer than tsplit cut into
+    pieces of at most that; one extent (ci, c, t0, t1) per piece, sorted by chunk c
     (stable: by cluster, then time), and ext_off[c] the first extent of
     chunk c. Reads the table back, so it is built once per table."""
     def build():
@@ -975,15 +975,15 @@ def _lbfgs_extents(chunk_tab, Mt):
         for ci, row in enumerate(ct):
             cuts = np.flatnonzero(np.diff(row)) + 1
             for a, b in zip(np.r_[0, cuts], np.r_[cuts, len(row)]):
-                ext += [(ci, int(row[a]), t0, min(t0 + LBFGS_TSPLIT, int(b)))
-                        for t0 in range(int(a), int(b), LBFGS_TSPLIT)]
+                ext += [(ci, int(row[a]), t0, min(t0 + tsplit, int(b)))
+                        for t0 in range(int(a), int(b), tsplit)]
         ext = np.array(ext, dtype=np.int32).reshape(-1, 4)
         ext = ext[np.argsort(ext[:, 1], kind='stable')]
         off = np.zeros(Mt + 1, dtype=np.int32)
         off[1:] = np.cumsum(np.bincount(ext[:, 1], minlength=Mt))
         return tuple(torch.from_numpy(a).to(chunk_tab.device)
                      for a in (ext, off))
-    return _table_memo('ext', chunk_tab, (Mt, LBFGS_TSPLIT), build)
+    return _table_memo('ext', chunk_tab, (Mt, tsplit), build)
 
 
 def _lbfgs_stations(pairs, N):
@@ -1224,6 +1224,59 @@ def rtr_tcg(JtJ, Jtr, J, iw, delta, maxit=12, kappa=0.01):
     return tuple(_ext().rtr_tcg(f32(JtJ), f32(Jtr),
                                 J.to(torch.complex64).contiguous(), f32(iw),
                                 f32(delta), int(maxit), float(kappa)))
+
+
+LEVERAGE_TSPLIT = 64  # most timeslots of one piece of k_leverage
+
+
+def leverage_rows(cohs, J, Hinv, chunk_tab, pairs, weights=None):
+    """The influence-map leverage of every cluster in one launch of
+    k_leverage (leverage.hip): cohs [M, R, 2, 2] and J [Mt, N, 2, 2] complex,
+    read as complex64, Hinv [Mt, 8N, 8N] the float64 inverse of the damped
+    JtJ of every chunk, chunk_tab [M, T] global chunk id of each (cluster,
+    timeslot), pairs [Nbase, 2] in any order and either way round,
+    R = T * Nbase, weights [R] or None. Returns lev [M, R] float64, computed
+    in float64; a row whose pair has a negative entry gets 0. Bitwise the
+    same from call to call. The first call with a new pair or chunk table
+    reads it back, for the bounds check and the pieces; after that the path
+    has no host synchronisation."""
+    dev = cohs.device
+    if cohs.dim() != 4 or tuple(cohs.shape[2:]) != (2, 2):
+        raise ValueError(f"cohs must be [M, R, 2, 2], got {tuple(cohs.shape)}")
+    M, R = int(cohs.shape[0]), int(cohs.shape[1])
+    if J.dim() != 4 or tuple(J.shape[2:]) != (2, 2) or J.shape[0] < 1 \
+            or J.shape[1] < 1:
+        raise ValueError("J must be [Mt, N, 2, 2]")
+    Mt, N = int(J.shape[0]), int(J.shape[1])
+    if tuple(Hinv.shape) != (Mt, 8 * N, 8 * N):
+        raise ValueError(f"Hinv must be [{Mt}, {8 * N}, {8 * N}], got "
+                         f"{tuple(Hinv.shape)}")
+    if chunk_tab.dim() != 2 or chunk_tab.shape[0] != M:
+        raise ValueError(f"chunk_tab must be [{M}, T]")
+    if pairs.dim() != 2 or pairs.shape[1] != 2 \
+            or chunk_tab.shape[1] * pairs.shape[0] != R:
+        raise ValueError("pairs must be [Nbase, 2] with T * Nbase rows")
+    if weights is not None and tuple(weights.shape) != (R,):
+        raise ValueError(f"weights must be [{R}]")
+    if M == 0 or R == 0:
+        return torch.zeros(M, R, dtype=torch.float64, device=dev)
+    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
+    chunk_tab, pairs = i32(chunk_tab), i32(pairs)
+    # the kernel indexes J and Hinv by both tables with no checks of its own
+    if _pair_range(pairs)[1] >= N:
+        raise ValueError(f"pairs name a station outside the {N} of J")
+    lo, hi = _pair_range(chunk_tab)
+    if lo < 0 or hi >= Mt:
+        raise ValueError(f"chunk_tab names chunks {lo}..{hi}, J has {Mt}")
+    pieces, _ = _lbfgs_extents(chunk_tab, Mt, LEVERAGE_TSPLIT)
+
+    def c64(t, *shape):
+        t = t.to(torch.complex64).reshape(*shape).contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+    f64 = lambda t: t.to(device=dev, dtype=torch.float64).contiguous()
+    return _ext().leverage_rows(
+        c64(cohs, M, R, 4), c64(J, Mt, N, 4), f64(Hinv),
+        None if weights is None else f64(weights), chunk_tab, pairs, pieces)
 
 
 _chol_scratch = {}
