@@ -353,6 +353,56 @@ def chol_blocked_on():
             and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
 
 
+def inverse_kernel_on():
+    """SAGECAL_INVERSE_KERNEL=1 opts diagnostics.leverage and
+    diagnostics.influence_map into the float64 inverse kernels of
+    spd_inverse.hip on device tensors; off by default, and
+    SAGECAL_FORCE_REFERENCE=1 overrides it."""
+    return (os.environ.get('SAGECAL_INVERSE_KERNEL') == '1'
+            and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
+
+
+INVERSE_SPLIT_ENTRIES = 1 << 23   # most matrix entries of one linalg.inv call
+INVERSE_KERNEL_MAXN = 1024        # SPD_INVERSE_MAXN of launchers.h
+
+
+def spd_inverse_torch(JtJ, mu):
+    """inv(JtJ + mu I) per matrix, in float64, by torch.linalg.inv. Batches
+    of at most 2^23 matrix entries (32 chunks of 64 stations) go to it at a
+    time: on the MI355X its batched triangular solve ran out of workspace
+    and raised for 160 matrices of 512, while 4 to 64 at a time all gave the
+    same bits in the same 0.31 to 0.34 s."""
+    n = JtJ.shape[-1]
+    if torch.is_tensor(mu):
+        mu = mu.to(device=JtJ.device, dtype=torch.float64).reshape(-1, 1, 1)
+    A = JtJ.to(torch.float64) + mu * torch.eye(n, dtype=torch.float64,
+                                               device=JtJ.device)
+    step = max(1, INVERSE_SPLIT_ENTRIES // (n * n))
+    if A.shape[0] <= step:
+        return torch.linalg.inv(A)
+    return torch.cat([torch.linalg.inv(A[i:i + step])
+                      for i in range(0, A.shape[0], step)])
+
+
+def spd_inverse_damped(JtJ, mu):
+    """X [Mt, n, n] float64 = (JtJ + mu I)^-1 for symmetric positive
+    definite JtJ + mu I: JtJ [Mt, n, n] float32 or float64, mu a number or a
+    tensor of one value or one per matrix. On the GPU, for n a multiple of 8
+    in 8..1024, the kernels of spd_inverse.hip (blocked Cholesky, inverse of
+    the factor and its product with itself, in float64 on the matrix unit):
+    they read the lower triangle of JtJ, return X == X^T to the bit, the
+    same bits from call to call and in any batch, and all NaN for a matrix
+    that is not positive definite. Elsewhere, and for other n,
+    spd_inverse_torch, which raises for a singular matrix."""
+    n = int(JtJ.shape[-1])
+    if _use_hip(JtJ) and JtJ.dim() == 3 and JtJ.shape[0] >= 1 \
+            and n % 8 == 0 and 8 <= n <= INVERSE_KERNEL_MAXN \
+            and JtJ.dtype in (torch.float32, torch.float64):
+        from . import hip_host
+        return hip_host.spd_inverse_damped(JtJ, mu)
+    return spd_inverse_torch(JtJ, mu)
+
+
 def rtr_tcg(JtJ, Jtr, J, iw, delta, maxit=12, kappa=0.01):
     """The inner solve of one RTR outer iteration at J [n, N, 2, 2], from
     the normal equations JtJ [n, 8N, 8N], Jtr [n, 8N] in reference.vecR

@@ -1027,8 +1027,64 @@ torch::Tensor leverage_rows(
   return lev;
 }
 
+// Doubles of scratch spd_inverse needs for Mt matrices of n: W [Mt, n, n] and
+// the inverted diagonal blocks [Mt, ceil(n / 32), 2, 32, 32].
+static int64_t spd_inverse_scratch(int64_t Mt, int64_t n) {
+  return Mt * (n * n + (n + 31) / 32 * 2048);
+}
+
+// X = (A + mu I)^-1 in float64 (spd_inverse.hip): A [Mt, n, n] float32 or
+// float64, read as symmetric from its lower triangle, mu float64 of one
+// element or Mt, scratch float64 of spd_inverse_scratch(Mt, n) elements.
+// Returns (X [Mt, n, n] float64, info [Mt] int32); a matrix with a
+// non-positive pivot has info != 0 and X all NaN.
+std::vector<torch::Tensor> spd_inverse(torch::Tensor A, torch::Tensor mu,
+                                       torch::Tensor scratch) {
+  const torch::Device dev = A.device();
+  TORCH_CHECK(A.is_cuda() && A.is_contiguous() &&
+              (A.scalar_type() == torch::kFloat ||
+               A.scalar_type() == torch::kDouble),
+              "A must be a contiguous float32 or float64 device tensor");
+  TORCH_CHECK(A.dim() == 3 && A.size(0) >= 1 && A.size(1) == A.size(2),
+              "A must be [Mt, n, n] with Mt >= 1");
+  const int64_t Mt = A.size(0), n = A.size(1);
+  TORCH_CHECK(n >= 8 && n <= SPD_INVERSE_MAXN && n % 8 == 0,
+              "n must be a multiple of 8 in 8..", SPD_INVERSE_MAXN, ", got ",
+              n);
+  TORCH_CHECK(Mt < (int64_t(1) << 20), "too many matrices");
+  TORCH_CHECK(on_dev(mu, dev, torch::kDouble) &&
+              (mu.numel() == 1 || mu.numel() == Mt),
+              "mu must be contiguous float64 on the device, one element or "
+              "one per matrix");
+  TORCH_CHECK(on_dev(scratch, dev, torch::kDouble) &&
+              scratch.numel() >= spd_inverse_scratch(Mt, n),
+              "scratch must hold ", spd_inverse_scratch(Mt, n),
+              " float64 on the device");
+  check_aligned16({&A, &scratch}, "A and scratch");
+  auto X = torch::empty({Mt, n, n}, torch::dtype(torch::kDouble).device(dev));
+  auto info = torch::zeros({Mt}, torch::dtype(torch::kInt).device(dev));
+  SpdInverseArgs a = {};
+  a.A = A.data_ptr();
+  a.mu = dp(mu);
+  a.W = scratch.data_ptr<double>();
+  a.D = a.W + Mt * n * n;
+  a.info = info.data_ptr<int>();
+  a.Mt = (int)Mt; a.n = (int)n;
+  a.a_f64 = A.scalar_type() == torch::kDouble;
+  a.mu_stride = mu.numel() == 1 ? 0 : 1;
+  CHECK_HIP(launch_spd_inverse(a, X.data_ptr<double>(), cur_stream()));
+  return {X, info};
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("jtr_grad", &jtr_grad, "gradient-only accumulation (gfx950)");
+  m.attr("SPD_INVERSE_MAXN") = SPD_INVERSE_MAXN;
+  m.def("spd_inverse_scratch", &spd_inverse_scratch,
+        "float64 elements of scratch spd_inverse needs", py::arg("Mt"),
+        py::arg("n"));
+  m.def("spd_inverse", &spd_inverse,
+        "float64 inverse of damped SPD matrices (gfx950)", py::arg("A"),
+        py::arg("mu"), py::arg("scratch"));
   m.def("leverage_rows", &leverage_rows,
         "influence-map leverage, all clusters in one launch (gfx950)",
         py::arg("cohs"), py::arg("J"), py::arg("Hinv"), py::arg("wts"),

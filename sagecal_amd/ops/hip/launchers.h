@@ -181,7 +181,31 @@ struct LeverageArgs {
   int M, T, Nbase, N, Mt, E;
 };
 
+// The float64 inverse of damped SPD matrices (spd_inverse.hip), n a multiple
+// of 8 and nt = ceil(n / 32) blocks a side. All pointers 16-byte aligned.
+struct SpdInverseArgs {
+  const void* A;            // [Mt, n, n] float32 or float64 (a_f64); the
+                            // lower triangle is read, nothing is written
+  const double* mu;         // [1] or [Mt], added to the diagonal
+  double* W;                // scratch [Mt, n, n]
+  double* D;                // scratch [Mt, nt, 2, 32, 32]
+  int* info;                // [Mt], arrives zeroed
+  int Mt, n;
+  int a_f64;                // non-zero: A is float64
+  int mu_stride;            // 0: one mu for all; 1: one per matrix
+};
+
 extern "C" {
+
+// The largest n of launch_spd_inverse.
+#define SPD_INVERSE_MAXN 1024
+// X [Mt, n, n] = (A + mu I)^-1, both triangles written, X == X^T to the
+// bit. A non-positive pivot sets info[matrix] and fills that matrix of X
+// with NaN. Scratch contents are unspecified on entry and exit.
+// hipErrorInvalidValue: Mt < 1, n < 8, n > SPD_INVERSE_MAXN, n not a
+// multiple of 8, a null pointer, or mu_stride neither 0 nor 1.
+hipError_t launch_spd_inverse(SpdInverseArgs a, double* X,
+                              hipStream_t stream);
 
 // Threads per workgroup of k_leverage; a workgroup serves WAVE pairs.
 #define LEVERAGE_TB 256

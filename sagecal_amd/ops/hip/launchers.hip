@@ -10,6 +10,7 @@
 #include "joint_jtj.hip"
 #include "rtr_tcg.hip"
 #include "leverage.hip"
+#include "spd_inverse.hip"
 #include "cholesky.hip"
 #include "cholesky_blocked.hip"
 #include "element_beam.hip"
@@ -314,6 +315,48 @@ hipError_t launch_leverage(LeverageArgs a, double* lev, hipStream_t stream) {
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_leverage, dim3((a.Nbase + WAVE - 1) / WAVE, a.E),
                      dim3(LEVERAGE_TB), 0, stream, a, lev);
+  return hipGetLastError();
+}
+
+// potrf (two launches per 32 columns, the first pair reading A), trtri (one
+// per block column), lauum; one workgroup per 32 x 32 block
+// (spd_inverse.hip)
+hipError_t launch_spd_inverse(SpdInverseArgs a, double* X,
+                              hipStream_t stream) {
+  if (a.Mt < 1 || a.n < 8 || a.n > SPD_INVERSE_MAXN || a.n % 8 != 0 ||
+      a.A == nullptr || a.mu == nullptr || a.W == nullptr ||
+      a.D == nullptr || a.info == nullptr || X == nullptr ||
+      (a.mu_stride != 0 && a.mu_stride != 1))
+    return hipErrorInvalidValue;
+  const int nt = (a.n + SPD_NB - 1) / SPD_NB;
+  if ((long long)a.Mt * (nt * (nt + 1) / 2) > 0x7fffffffLL)
+    return hipErrorInvalidValue;
+  const dim3 tb(SPD_TB);
+  for (int kb = 0; kb < nt; ++kb) {
+    const int k = kb * SPD_NB, nb = nt - kb - 1;
+    const dim3 gp(a.Mt * (nb > 0 ? nb : 1));
+    const int ntiles = nb * (nb + 1) / 2;
+    const dim3 gs(a.Mt * ntiles);
+    if (kb > 0) {
+      hipLaunchKernelGGL(k_spdinv_panel, gp, tb, 0, stream, a, k, nb);
+      if (nb > 0)
+        hipLaunchKernelGGL(k_spdinv_syrk, gs, tb, 0, stream, a, k, ntiles);
+    } else if (a.a_f64) {
+      hipLaunchKernelGGL(k_spdinv_panel_f64, gp, tb, 0, stream, a, k, nb);
+      if (nb > 0)
+        hipLaunchKernelGGL(k_spdinv_syrk_f64, gs, tb, 0, stream, a, k,
+                           ntiles);
+    } else {
+      hipLaunchKernelGGL(k_spdinv_panel_f32, gp, tb, 0, stream, a, k, nb);
+      if (nb > 0)
+        hipLaunchKernelGGL(k_spdinv_syrk_f32, gs, tb, 0, stream, a, k,
+                           ntiles);
+    }
+  }
+  for (int I = 1; I < nt; ++I)
+    hipLaunchKernelGGL(k_spdinv_trtri, dim3(a.Mt * I), tb, 0, stream, a, I);
+  hipLaunchKernelGGL(k_spdinv_lauum, dim3(a.Mt * (nt * (nt + 1) / 2)), tb, 0,
+                     stream, a, X);
   return hipGetLastError();
 }
 

@@ -1279,6 +1279,50 @@ def leverage_rows(cohs, J, Hinv, chunk_tab, pairs, weights=None):
         None if weights is None else f64(weights), chunk_tab, pairs, pieces)
 
 
+_spd_scratch = {}
+
+
+def spd_inverse_damped(JtJ, mu, return_info=False):
+    """X = (JtJ + mu I)^-1 [Mt, n, n] in float64 through the kernels of
+    spd_inverse.hip: JtJ [Mt, n, n] float32 or float64 on the device, read
+    as symmetric from its lower triangle and left as it is, n a multiple of
+    8 up to SPD_INVERSE_MAXN; mu a number or a tensor of one value or one
+    per matrix. X == X^T to the bit, the same from call to call and whatever
+    the batch a matrix comes in. A matrix that is not positive definite
+    comes back all NaN; the flags info [Mt] int32 (non-zero: failed) stay
+    on the device and come along with return_info=True as (X, info). The
+    path has no host synchronisation."""
+    ext = _ext()
+    if JtJ.dim() != 3 or JtJ.shape[0] < 1 or JtJ.shape[1] != JtJ.shape[2]:
+        raise ValueError(f"JtJ must be [Mt, n, n], got {tuple(JtJ.shape)}")
+    Mt, n = int(JtJ.shape[0]), int(JtJ.shape[1])
+    if n < 8 or n % 8 or n > ext.SPD_INVERSE_MAXN:
+        raise ValueError(f"n must be a multiple of 8 in 8.."
+                         f"{ext.SPD_INVERSE_MAXN}, got {n}")
+    if JtJ.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"JtJ must be float32 or float64, got {JtJ.dtype}")
+    dev = JtJ.device
+    if torch.is_tensor(mu):
+        mu = mu.to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+        if mu.numel() not in (1, Mt):
+            raise ValueError(f"mu must hold 1 or {Mt} values, got "
+                             f"{mu.numel()}")
+    else:
+        mu = torch.full((1,), float(mu), dtype=torch.float64, device=dev)
+    key = (Mt, n, str(dev))
+    sc = _spd_scratch.get(key)
+    if sc is None:
+        sc = dispatch.remember(
+            _spd_scratch, key,
+            torch.empty(ext.spd_inverse_scratch(Mt, n), dtype=torch.float64,
+                        device=dev), 4)
+    A = JtJ.contiguous()
+    if A.data_ptr() % 16:
+        A = A.clone()
+    X, info = ext.spd_inverse(A, mu, sc)
+    return (X, info) if return_info else X
+
+
 _chol_scratch = {}
 
 

@@ -23,19 +23,24 @@ from ..ops import reference as R
 
 
 def _damped_inverse(JtJ, mu):
-    """inv(JtJ + mu I) per chunk, in float64. Batches of at most 2^23
-    matrix entries (32 chunks of 64 stations) go to torch.linalg.inv at a
-    time: on the MI355X its batched triangular solve ran out of workspace
-    and raised for 160 matrices of 512, while 4 to 64 at a time all gave the
-    same bits in the same 0.31 to 0.34 s."""
-    n = JtJ.shape[-1]
-    A = JtJ.to(torch.float64) + mu * torch.eye(n, dtype=torch.float64,
-                                               device=JtJ.device)
-    step = max(1, (1 << 23) // (n * n))
-    if A.shape[0] <= step:
-        return torch.linalg.inv(A)
-    return torch.cat([torch.linalg.inv(A[i:i + step])
-                      for i in range(0, A.shape[0], step)])
+    """inv(JtJ + mu I) per chunk, in float64: torch.linalg.inv
+    (ops.spd_inverse_torch), or with SAGECAL_INVERSE_KERNEL=1 the public
+    ops.spd_inverse_damped, which on device tensors runs the kernels of
+    spd_inverse.hip. Those are a Cholesky and return NaN for a chunk whose
+    JtJ + mu I is not positive definite, which the float32 JtJ at mu = 1e-6
+    often is not: its gauge direction has eigenvalue 0 up to rounding. Such
+    chunks are inverted by torch.linalg.inv as before (an LU, indifferent to
+    the sign of that eigenvalue, which the leverage does not see); finding
+    them reads one flag per chunk back to the host."""
+    if not ops.inverse_kernel_on():
+        return ops.spd_inverse_torch(JtJ, mu)
+    X = ops.spd_inverse_damped(JtJ, mu)
+    bad = torch.isnan(X[:, 0, 0])
+    if bool(bad.any()):
+        per_chunk = torch.is_tensor(mu) and mu.numel() > 1
+        X[bad] = ops.spd_inverse_torch(
+            JtJ[bad], mu.reshape(-1)[bad.to(mu.device)] if per_chunk else mu)
+    return X
 
 
 def leverage(x, coh, J, bb, N, weights=None, chunk_rows=None, nchunk=1,

@@ -11,7 +11,18 @@ the kernel path (T and Nbase given), the torch path of ops.leverage_rows
 that diagnostics.leverage does without T and Nbase (about 34 GB). Shape (b):
 64 stations, 960 timeslots, 10 clusters of 16 chunks (1,935,360 rows), kernel
 only. Device events around each call, the paths alternating after warm-up,
-the median of 10 with its spread and the peak memory; needs a GPU."""
+the median of 10 with its spread and the peak memory; needs a GPU.
+
+    python tools/bench_leverage.py --sections b_bench_default,c_ten_chunks \
+        --out profiles/spd_inverse.json
+
+also times the float64 inverse kernels of spd_inverse.hip
+(ops.spd_inverse_damped) next to torch.linalg.inv in shape (b), 160 matrices
+of 512 from the float32 JtJ, and in shape (c), the 10 matrices of one chunk
+per cluster; at mu = 1e-6 as the diagnostic sets it and at 1e-2, with the
+number of matrices the kernels flag as not positive definite (their last
+kernel skips those, and the diagnostic sends them to torch.linalg.inv), and
+influence_map(cluster=None) with SAGECAL_INVERSE_KERNEL=1 and without."""
 import argparse
 import json
 import os
@@ -91,6 +102,32 @@ def forced_reference(fn):
     return run
 
 
+def with_inverse_kernel(fn):
+    def run():
+        os.environ['SAGECAL_INVERSE_KERNEL'] = '1'
+        try:
+            return fn()
+        finally:
+            os.environ.pop('SAGECAL_INVERSE_KERNEL')
+    return run
+
+
+def inverse_paths(JtJ):
+    """The callables that invert JtJ + mu I, and what the kernels flag."""
+    fns = {'inverse_float64': lambda: diag._damped_inverse(JtJ, 1e-6),
+           'inverse_kernels': lambda: ops.spd_inverse_damped(JtJ, 1e-6),
+           'inverse_float64_mu1e-2': lambda: ops.spd_inverse_torch(JtJ, 1e-2),
+           'inverse_kernels_mu1e-2': lambda: ops.spd_inverse_damped(JtJ,
+                                                                    1e-2)}
+    flagged = {f'mu{mu:g}': int(hip_host.spd_inverse_damped(
+        JtJ, mu, return_info=True)[1].count_nonzero()) for mu in (1e-6, 1e-2)}
+    ref, X = fns['inverse_float64_mu1e-2'](), fns['inverse_kernels_mu1e-2']()
+    return fns, {'matrices': int(JtJ.shape[0]), 'n': int(JtJ.shape[1]),
+                 'kernels_flag_not_positive_definite': flagged,
+                 'max_abs_diff_mu1e-2': float((X - ref).abs().max()),
+                 'max_abs_inverse_mu1e-2': float(ref.abs().max())}
+
+
 def shape_a(args):
     T = 8
     state, cohs, tile, bb = make(T, [1])
@@ -124,14 +161,18 @@ def shape_b(args):
                         rows, K, lay)[0] for ci in range(M)])
     JtJ = assemble()
     Hinv = diag._damped_inverse(JtJ, 1e-6)
+    inv_fns, inv_facts = inverse_paths(JtJ)
+    imap = lambda: diag.influence_map(state, cohs, tile, bb, cluster=None,
+                                      layout=lay)
     out = compare({
-        'jtj_assembly': assemble,
-        'inverse_float64': lambda: diag._damped_inverse(JtJ, 1e-6),
+        'jtj_assembly': assemble, **inv_fns,
         'k_leverage': lambda: ops.leverage_rows(cohs, state.J, Hinv, tab,
                                                 pairs),
-        'influence_map_all_clusters': lambda: diag.influence_map(
-            state, cohs, tile, bb, cluster=None, layout=lay)},
+        'influence_map_all_clusters': imap,
+        'influence_map_all_clusters_inverse_kernels':
+            with_inverse_kernel(imap)},
         args.warmup, args.runs)
+    out['inverse'] = inv_facts
     lev = diag.influence_map(state, cohs, tile, bb, cluster=None, layout=lay)
     out['lev_min_max'] = [float(lev.min()), float(lev.max())]
     # coh in, lev out, and per (pair, chunk) the 8x8 block Hpq and the two
@@ -144,9 +185,25 @@ def shape_b(args):
     return out
 
 
+def shape_c(args):
+    """One chunk per cluster: the 10 matrices of 512 that the leverage of
+    single clusters inverts, from the same data as shape (b)."""
+    T, M = 960, 10
+    state, cohs, tile, bb = make(T, [1] * M)
+    lay = hip_host.BaselineLayout(bb, tile.Nbase, T, 1, N, DEV)
+    JtJ = torch.cat([
+        ops.jtj_jtr(tile.x, cohs[ci], state.cluster_J(ci), bb, N, None,
+                    None, 1, lay)[0] for ci in range(M)])
+    fns, facts = inverse_paths(JtJ)
+    out = compare(fns, args.warmup, args.runs)
+    out['inverse'] = facts
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='profiles/leverage.json')
+    ap.add_argument('--sections', default='a_one_cluster_T8,b_bench_default')
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--runs', type=int, default=10)
     args = ap.parse_args()
@@ -155,7 +212,10 @@ def main():
            'runs': args.runs, 'order': 'the paths of a shape in turn, '
            'repeated', 'device': 'MI355X (gfx950)', 'N': N}
     for name, fn in (('a_one_cluster_T8', shape_a),
-                     ('b_bench_default', shape_b)):
+                     ('b_bench_default', shape_b),
+                     ('c_ten_chunks', shape_c)):
+        if name not in args.sections.split(','):
+            continue
         res[name] = fn(args)
         print(json.dumps({name: res[name]}), flush=True)
     os.makedirs(os.path.dirname(args.out) or '.', exist_ok=True)
