@@ -256,7 +256,8 @@ def _diffuse_hook(args, pack, tile, bb):
     def hook(adm, cohs):
         out = adm.diffuse_coherencies(tile.u, tile.v, tile.w, bb, Cm,
                                       beta_c, lmn, tile.freq0,
-                                      tile.fdelta)
+                                      tile.fdelta, T=tile.tilesz,
+                                      Nbase=tile.Nbase)
         if out is not None:
             cohs[ci] = out.to(device=cohs.device, dtype=cohs.dtype)
     return hook

@@ -364,14 +364,22 @@ class ConsensusADMM:
         return Zband * C0, beta / (2.0 * np.pi)
 
     def diffuse_coherencies(self, u, v, w, bb, Cm, beta_c, lmn, freq,
-                            fdelta):
+                            fdelta, T=None, Nbase=None):
         """Diffuse-cluster coherencies with the spatial model applied
         (recalculate_diffuse_coherencies, diffuse_predict.c:295):
-        Zp C Zq^H per baseline via Jones shapelet products."""
+        Zp C Zq^H per baseline via Jones shapelet products. With
+        SAGECAL_DIFFUSE_KERNEL=1, u on the device and rows r = t*Nbase + b
+        (T and Nbase given), ops.diffuse_coherencies and a device tensor."""
         from .. import shapelet as shmod
+        from ..ops import dispatch as ops
         Z, bz = self.diffuse_station_series()
         if Z is None:
             return None
+        if ops.diffuse_kernel_on() and u.is_cuda and T is not None \
+                and Nbase is not None and u.shape[0] == T * Nbase:
+            return ops.diffuse_coherencies(
+                u, v, w, ops.lbfgs_pair_table(bb, Nbase, u.device), T, Z, bz,
+                Cm, beta_c, lmn, freq, fdelta)
         ll, mm, nn1 = lmn
         return shmod.recalculate_diffuse_coherencies(
             u.cpu().double(), v.cpu().double(), w.cpu().double(),

@@ -7,6 +7,7 @@ round-end check verifies the native .so is actually loaded).
 Set SAGECAL_FORCE_REFERENCE=1 to explicitly run the torch reference on GPU
 (used only for kernel A/B numerics tests).
 """
+import math
 import os
 import torch
 
@@ -479,6 +480,59 @@ def leverage_rows(cohs, J, Hinv, chunk_tab, pairs, weights=None):
     if weights is not None:
         lev = lev * weights.to(device=dev, dtype=torch.float64)
     return lev
+
+
+def diffuse_kernel_on():
+    """SAGECAL_DIFFUSE_KERNEL=1 opts ConsensusADMM.diffuse_coherencies, the
+    diffuse hook of sagecal-mpi -D, into the kernels of diffuse.hip on device
+    tensors; off by default, and SAGECAL_FORCE_REFERENCE=1 overrides it."""
+    return (os.environ.get('SAGECAL_DIFFUSE_KERNEL') == '1'
+            and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
+
+
+DIFFUSE_KERNEL_MAX_GZ = 4     # DIFFUSE_MAX_GZ and DIFFUSE_MAX_N2 of launchers.h
+DIFFUSE_KERNEL_MAX_N2 = 32
+
+
+def diffuse_coherencies(u, v, w, pairs, T, Z, beta_z, Cm, beta_c, lmn, freq,
+                        fdelta):
+    """Coherencies V [T * Nbase, 2, 2] of a diffuse shapelet cluster with the
+    per-station spatial model applied, shapelet.recalculate_diffuse_
+    coherencies on structured rows: with (p, q) = pairs[b], row r = t*Nbase
+    + b, n1 = Gc + Gz - 1, n2 = Gz + n1 - 1, g1 = product_scale(beta_c,
+    beta_z) and g2 = product_scale(beta_z, g1),
+      H_pq = Z_p x (C x Z_q^H)     (Jones series products, n2 x n2 modes)
+      V_r = 2 pi sum_kl basis_kl(-u_r f, v_r f; g2) H_pq[k,l]
+            * exp(i 2 pi f (u_r l + v_r m + w_r (n-1)))
+            * |sinc(pi fdelta (u_r l + v_r m + w_r (n-1)))|
+    u, v, w [T * Nbase] in seconds, pairs [Nbase, 2] (the table of
+    lbfgs_pair_table), Z [N, Gz*Gz, 2, 2] at scale beta_z, Cm [Gc*Gc, 2, 2]
+    at scale beta_c, lmn = (l, m, n - 1) of the cluster, freq and fdelta in
+    Hz; a row whose pair has a negative entry gets zeros. On the GPU, for
+    Gz <= 4 and n2 <= 32, the two kernels of diffuse.hip: series products in
+    float64 on the matrix unit, the mode sum in float32, complex64 out, the
+    same bits from call to call. Elsewhere, and for larger series, the host
+    function in complex128 on rows expanded from the table, its result
+    moved to the device of u."""
+    Gz, Gc = math.isqrt(Z.shape[1]), math.isqrt(Cm.shape[0])
+    Nbase = int(pairs.shape[0])
+    if tuple(u.shape) != (int(T) * Nbase,):
+        raise ValueError(f"u must be [T * Nbase] = [{int(T) * Nbase}], got "
+                         f"{tuple(u.shape)}")
+    if _use_hip(u) and Gz <= DIFFUSE_KERNEL_MAX_GZ \
+            and Gc + 2 * Gz - 2 <= DIFFUSE_KERNEL_MAX_N2:
+        from . import hip_host
+        return hip_host.diffuse_coherencies(u, v, w, pairs, T, Z, beta_z, Cm,
+                                            beta_c, lmn, freq, fdelta)
+    from .. import shapelet
+    pr = pairs.to(device='cpu', dtype=torch.long)
+    live = (pr >= 0).all(dim=1).repeat(int(T))
+    f64 = lambda t: t.to(device='cpu', dtype=torch.float64)
+    out = shapelet.recalculate_diffuse_coherencies(
+        f64(u), f64(v), f64(w), pr.clamp_min(0).repeat(int(T), 1), Z.cpu(),
+        beta_z, Cm.cpu(), beta_c, *lmn, freq, fdelta)
+    out = torch.where(live[:, None, None], out, out.new_zeros(()))
+    return out.to(u.device)
 
 
 def _joint_blocks(chunk_off, nchunks, blocked):

@@ -1076,8 +1076,77 @@ std::vector<torch::Tensor> spd_inverse(torch::Tensor A, torch::Tensor mu,
   return {X, info};
 }
 
+// The diffuse-cluster coherencies with the spatial model applied
+// (diffuse.hip): u, v, w [R] float64 with R == T * Nbase, pairs [Nbase, 2]
+// int32, Z [N, Gz*Gz, 2, 2] and Cm [Gc*Gc, 2, 2] complex128, T1 [n1, Gc, Gz]
+// and T2 [n2, Gz, n1] float64, n1 = Gc + Gz - 1, n2 = Gz + n1 - 1. Returns
+// [R, 2, 2] complex64. The caller guarantees pair entries below N.
+torch::Tensor diffuse_coherencies(
+    torch::Tensor u, torch::Tensor v, torch::Tensor w, torch::Tensor pairs,
+    int64_t T, torch::Tensor Z, torch::Tensor Cm, torch::Tensor T1,
+    torch::Tensor T2, double g2, double ll, double mm, double nn1,
+    double freq, double fdelta2) {
+  const torch::Device dev = u.device();
+  TORCH_CHECK(on_dev(pairs, dev, torch::kInt) && pairs.dim() == 2 &&
+              pairs.size(0) >= 1 && pairs.size(1) == 2,
+              "pairs must be contiguous [Nbase, 2] int32 on the device");
+  const int64_t Nbase = pairs.size(0), R = T * Nbase;
+  TORCH_CHECK(T >= 1 && T < (int64_t(1) << 31) &&
+              Nbase < (int64_t(1) << 31), "rows out of range");
+  for (const torch::Tensor* t : {&u, &v, &w})
+    TORCH_CHECK(on_dev(*t, dev, torch::kDouble, R) && t->dim() == 1,
+                "u, v, w must be contiguous [T * Nbase] float64 on the "
+                "device");
+  TORCH_CHECK(on_dev(T1, dev, torch::kDouble) && T1.dim() == 3 &&
+              on_dev(T2, dev, torch::kDouble) && T2.dim() == 3,
+              "T1 and T2 must be contiguous 3-D float64 on the device");
+  const int64_t n1 = T1.size(0), Gc = T1.size(1), Gz = T1.size(2);
+  const int64_t n2 = T2.size(0);
+  TORCH_CHECK(Gc >= 1 && Gz >= 1 && n1 == Gc + Gz - 1 && n2 == Gz + n1 - 1 &&
+              T2.size(1) == Gz && T2.size(2) == n1,
+              "T1 must be [n1, Gc, Gz] and T2 [n2, Gz, n1]");
+  TORCH_CHECK(Gz <= DIFFUSE_MAX_GZ && n2 <= DIFFUSE_MAX_N2,
+              "the diffuse kernels take Gz <= ", DIFFUSE_MAX_GZ,
+              " and n2 <= ", DIFFUSE_MAX_N2, ", got ", Gz, " and ", n2);
+  TORCH_CHECK(on_dev(Z, dev, torch::kComplexDouble) && Z.dim() == 4 &&
+              Z.size(0) >= 1 && Z.size(0) <= 65535 &&
+              Z.size(1) == Gz * Gz && Z.size(2) == 2 && Z.size(3) == 2,
+              "Z must be contiguous [N, Gz*Gz, 2, 2] complex128, N <= 65535");
+  TORCH_CHECK(on_dev(Cm, dev, torch::kComplexDouble, Gc * Gc * 4) &&
+              Cm.dim() == 3, "Cm must be contiguous [Gc*Gc, 2, 2] complex128");
+  const int64_t N = Z.size(0);
+  const int64_t RA = DIFFUSE_PAD16(2 * n2), RB = DIFFUSE_PAD16(4 * n2),
+                Kp = DIFFUSE_PAD16(4 * n1 * Gz);
+  auto scratch = torch::empty({N * (RA + RB) * Kp},
+                              torch::dtype(torch::kDouble).device(dev));
+  auto out = torch::empty({R, 2, 2},
+                          torch::dtype(torch::kComplexFloat).device(dev));
+  check_aligned16({&Z, &Cm, &scratch, &out}, "Z, Cm, scratch and out");
+  DiffuseArgs a = {};
+  a.u = dp(u); a.v = dp(v); a.w = dp(w); a.pairs = ip(pairs);
+  a.Z = reinterpret_cast<const double2*>(Z.data_ptr());
+  a.C = reinterpret_cast<const double2*>(Cm.data_ptr());
+  a.T1 = dp(T1); a.T2 = dp(T2);
+  a.A = scratch.data_ptr<double>();
+  a.B = a.A + N * RA * Kp;
+  a.T = (int)T; a.Nbase = (int)Nbase; a.N = (int)N;
+  a.Gz = (int)Gz; a.Gc = (int)Gc;
+  a.g2 = g2; a.ll = ll; a.mm = mm; a.nn1 = nn1;
+  a.freq = freq; a.fdelta2 = fdelta2;
+  CHECK_HIP(launch_diffuse(a, cptr(out), cur_stream()));
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("jtr_grad", &jtr_grad, "gradient-only accumulation (gfx950)");
+  m.attr("DIFFUSE_MAX_GZ") = DIFFUSE_MAX_GZ;
+  m.attr("DIFFUSE_MAX_N2") = DIFFUSE_MAX_N2;
+  m.def("diffuse_coherencies", &diffuse_coherencies,
+        "diffuse-cluster predict with the spatial model (gfx950)",
+        py::arg("u"), py::arg("v"), py::arg("w"), py::arg("pairs"),
+        py::arg("T"), py::arg("Z"), py::arg("Cm"), py::arg("T1"),
+        py::arg("T2"), py::arg("g2"), py::arg("ll"), py::arg("mm"),
+        py::arg("nn1"), py::arg("freq"), py::arg("fdelta2"));
   m.attr("SPD_INVERSE_MAXN") = SPD_INVERSE_MAXN;
   m.def("spd_inverse_scratch", &spd_inverse_scratch,
         "float64 elements of scratch spd_inverse needs", py::arg("Mt"),

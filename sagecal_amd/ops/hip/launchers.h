@@ -195,7 +195,40 @@ struct SpdInverseArgs {
   int mu_stride;            // 0: one mu for all; 1: one per matrix
 };
 
+// The diffuse-cluster predict with the spatial model (diffuse.hip). Rows
+// r = t*Nbase + b, R = T*Nbase; n1 = Gc + Gz - 1, n2 = Gz + n1 - 1. The host
+// guarantees pair entries below N (negative: the row gets zeros). All
+// pointers 16-byte aligned.
+struct DiffuseArgs {
+  const double *u, *v, *w;  // [R] seconds
+  const int* pairs;         // [Nbase, 2]
+  const double2* Z;         // [N, Gz*Gz, 4] station series
+  const double2* C;         // [Gc*Gc, 4] sky series
+  const double* T1;         // [n1, Gc, Gz] product tensor of C x Z^H
+  const double* T2;         // [n2, Gz, n1] product tensor of Z x (C Z^H)
+  double* A;                // scratch [N, RA, Kp], RA = DIFFUSE_PAD16(2 n2),
+                            // Kp = DIFFUSE_PAD16(4 n1 Gz)
+  double* B;                // scratch [N, RB, Kp], RB = DIFFUSE_PAD16(4 n2)
+  int T, Nbase, N, Gz, Gc;
+  double g2;                // scale of the product series
+  double ll, mm, nn1;       // direction of the cluster
+  double freq, fdelta2;     // channel [Hz] and its halfwidth
+};
+
 extern "C" {
+
+// The supported range of launch_diffuse: the pair kernel keeps H_pq, n2 x n2
+// 2x2 complex64 blocks, in 32 KB of LDS, over the 27 KB in which it staged
+// the operands of the product, and covers the 2 n2 rows of that product with
+// the four 16-row tiles of its four waves; the station kernel's LDS holds
+// Gz x Gc <= DIFFUSE_MAX_GZ x DIFFUSE_MAX_N2 blocks.
+#define DIFFUSE_MAX_GZ 4
+#define DIFFUSE_MAX_N2 32
+#define DIFFUSE_PAD16(x) (((x) + 15) / 16 * 16)
+// out [R, 4] complex64, fully written; the scratch is fully written before
+// it is read. hipErrorInvalidValue: a dimension < 1, Gz > DIFFUSE_MAX_GZ,
+// n2 > DIFFUSE_MAX_N2, N > 65535 or a null pointer.
+hipError_t launch_diffuse(DiffuseArgs a, float2* out, hipStream_t stream);
 
 // The largest n of launch_spd_inverse.
 #define SPD_INVERSE_MAXN 1024

@@ -11,6 +11,7 @@
 #include "rtr_tcg.hip"
 #include "leverage.hip"
 #include "spd_inverse.hip"
+#include "diffuse.hip"
 #include "cholesky.hip"
 #include "cholesky_blocked.hip"
 #include "element_beam.hip"
@@ -315,6 +316,24 @@ hipError_t launch_leverage(LeverageArgs a, double* lev, hipStream_t stream) {
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_leverage, dim3((a.Nbase + WAVE - 1) / WAVE, a.E),
                      dim3(LEVERAGE_TB), 0, stream, a, lev);
+  return hipGetLastError();
+}
+
+// the per-station operands (a workgroup per station and row of C Z^H, one
+// more per station for Z's half), then a workgroup per pair (diffuse.hip)
+hipError_t launch_diffuse(DiffuseArgs a, float2* out, hipStream_t stream) {
+  if (a.T < 1 || a.Nbase < 1 || a.N < 1 || a.N > 65535 || a.Gz < 1 ||
+      a.Gz > DIFFUSE_MAX_GZ || a.Gc < 1 ||
+      a.Gc + 2 * a.Gz - 2 > DIFFUSE_MAX_N2 || a.u == nullptr ||
+      a.v == nullptr || a.w == nullptr || a.pairs == nullptr ||
+      a.Z == nullptr || a.C == nullptr || a.T1 == nullptr ||
+      a.T2 == nullptr || a.A == nullptr || a.B == nullptr || out == nullptr)
+    return hipErrorInvalidValue;
+  const int n1 = a.Gc + a.Gz - 1;
+  hipLaunchKernelGGL(k_diffuse_station, dim3(a.N, n1 + 1), dim3(DIF_TB), 0,
+                     stream, a);
+  hipLaunchKernelGGL(k_diffuse_pair, dim3(a.Nbase), dim3(DIF_TB), 0, stream,
+                     a, out);
   return hipGetLastError();
 }
 

@@ -1323,6 +1323,77 @@ def spd_inverse_damped(JtJ, mu, return_info=False):
     return (X, info) if return_info else X
 
 
+DIFFUSE_MAX_GZ = 4    # launchers.h
+DIFFUSE_MAX_N2 = 32
+
+_diffuse_tensors = {}
+
+
+def diffuse_product_tensors(Gc, Gz, beta_c, beta_z, dev):
+    """(T1 [n1, Gc, Gz], T2 [n2, Gz, n1], g2) of the two series products of
+    the diffuse predict, float64 on `dev`: the Gauss-Hermite quadrature of
+    shapelet.shapelet_product_tensor on the host, once per (Gc, Gz, beta_c,
+    beta_z, device)."""
+    from .. import shapelet
+    key = (int(Gc), int(Gz), float(beta_c), float(beta_z), str(dev))
+    hit = _diffuse_tensors.get(key)
+    if hit is None:
+        n1 = Gc + Gz - 1
+        n2 = Gz + n1 - 1
+        g1 = shapelet.product_scale(beta_c, beta_z)
+        g2 = shapelet.product_scale(beta_z, g1)
+        f64 = lambda t: t.to(device=dev, dtype=torch.float64).contiguous()
+        T1 = shapelet.shapelet_product_tensor(Gc, Gz, n1, beta_c, beta_z, g1)
+        T2 = shapelet.shapelet_product_tensor(Gz, n1, n2, beta_z, g1, g2)
+        hit = dispatch.remember(_diffuse_tensors, key,
+                                (f64(T1), f64(T2), g2), 8)
+    return hit
+
+
+def diffuse_coherencies(u, v, w, pairs, T, Z, beta_z, Cm, beta_c, lmn, freq,
+                        fdelta):
+    """The diffuse cluster's coherencies [T * Nbase, 2, 2] complex64 through
+    k_diffuse_station and k_diffuse_pair (diffuse.hip): u, v, w [T * Nbase]
+    on the device, pairs [Nbase, 2] in any order and either way round, Z
+    [N, Gz*Gz, 2, 2] and Cm [Gc*Gc, 2, 2] complex, read as complex128, with
+    Gz <= DIFFUSE_MAX_GZ and n2 = Gc + 2 Gz - 2 <= DIFFUSE_MAX_N2. The series
+    products run in float64, the mode sum in float32; a row whose pair has a
+    negative entry gets zeros. Bitwise the same from call to call. The first
+    call with a new pair table reads it back for the bounds check; after
+    that the path has no host synchronisation."""
+    dev = u.device
+    if Z.dim() != 4 or tuple(Z.shape[2:]) != (2, 2) or Z.shape[0] < 1:
+        raise ValueError(f"Z must be [N, Gz*Gz, 2, 2], got {tuple(Z.shape)}")
+    if Cm.dim() != 3 or tuple(Cm.shape[1:]) != (2, 2):
+        raise ValueError(f"Cm must be [Gc*Gc, 2, 2], got {tuple(Cm.shape)}")
+    N, Gz, Gc = int(Z.shape[0]), math.isqrt(Z.shape[1]), \
+        math.isqrt(Cm.shape[0])
+    if Gz < 1 or Gc < 1 or Gz * Gz != Z.shape[1] or Gc * Gc != Cm.shape[0]:
+        raise ValueError("Z and Cm must hold square mode grids")
+    if Gz > DIFFUSE_MAX_GZ or Gc + 2 * Gz - 2 > DIFFUSE_MAX_N2:
+        raise ValueError(f"the diffuse kernels take Gz <= {DIFFUSE_MAX_GZ} "
+                         f"and n2 <= {DIFFUSE_MAX_N2}, got Gz = {Gz}, n2 = "
+                         f"{Gc + 2 * Gz - 2}")
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1 \
+            or int(T) < 1 or tuple(u.shape) != (int(T) * pairs.shape[0],):
+        raise ValueError("pairs must be [Nbase, 2] and u [T * Nbase]")
+    pairs = pairs.to(device=dev, dtype=torch.int32).contiguous()
+    # the kernels index Z's operands by the table with no checks of their own
+    if _pair_range(pairs)[1] >= N:
+        raise ValueError(f"pairs name a station outside the {N} of Z")
+    T1, T2, g2 = diffuse_product_tensors(Gc, Gz, beta_c, beta_z, dev)
+    f64 = lambda t: t.to(device=dev, dtype=torch.float64).contiguous()
+
+    def c128(t):
+        t = t.to(device=dev, dtype=torch.complex128).contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+    ll, mm, nn1 = lmn
+    return _ext().diffuse_coherencies(
+        f64(u), f64(v), f64(w), pairs, int(T), c128(Z), c128(Cm), T1, T2,
+        float(g2), float(ll), float(mm), float(nn1), float(freq),
+        0.5 * float(fdelta))
+
+
 _chol_scratch = {}
 
 
