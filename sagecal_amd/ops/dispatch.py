@@ -482,6 +482,61 @@ def leverage_rows(cohs, J, Hinv, chunk_tab, pairs, weights=None):
     return lev
 
 
+def normal_f64_on():
+    """SAGECAL_NORMAL_F64=1 opts diagnostics.leverage and
+    diagnostics.influence_map into the float64 normal matrices of
+    normal_f64.hip on device tensors with structured rows; off by default,
+    and SAGECAL_FORCE_REFERENCE=1 overrides it."""
+    return (os.environ.get('SAGECAL_NORMAL_F64') == '1'
+            and os.environ.get('SAGECAL_FORCE_REFERENCE') != '1')
+
+
+def normal_matrices(cohs, J, chunk_tab, pairs, weights=None):
+    """JtJ [Mt, 8N, 8N] float64, the Gauss-Newton normal matrix of every
+    chunk of every cluster: with (p, q) = pairs[b], c = chunk_tab[ci, t] and
+    row r = t*Nbase + b, G1 = C J_q^H, K = J_p C, D1 =
+    diagnostics._lin_blocks(G1) and D2 = diagnostics._anti_blocks(K),
+      JtJ[c] = sum over the rows of c of weights[r] [D1 D2]^T [D1 D2]
+    scattered to stations (p, q) in reference.vecR order, what
+    reference.jtj_jtr assembles; it does not depend on the data. cohs
+    [M, R, 2, 2], J [Mt, N, 2, 2], chunk_tab [M, T] global chunk ids, pairs
+    [Nbase, 2], R = T * Nbase, weights [R] or None; a pair with a negative
+    entry adds nothing. On the GPU the two kernels of normal_f64.hip, in
+    float64 on complex64 inputs (each pair at most once in the table);
+    elsewhere reference.jtj_jtr on complex128 upcasts, cluster by cluster."""
+    if _use_hip(cohs):
+        from . import hip_host
+        return hip_host.normal_matrices(cohs, J, chunk_tab, pairs, weights)
+    if cohs.dim() != 4 or J.dim() != 4 or chunk_tab.dim() != 2 \
+            or pairs.dim() != 2:
+        raise ValueError("cohs [M, R, 2, 2], J [Mt, N, 2, 2], chunk_tab "
+                         "[M, T] and pairs [Nbase, 2]")
+    M, Rn = int(cohs.shape[0]), int(cohs.shape[1])
+    T, Nbase = int(chunk_tab.shape[1]), int(pairs.shape[0])
+    Mt, N = int(J.shape[0]), int(J.shape[1])
+    if tuple(cohs.shape) != (M, Rn, 2, 2) or chunk_tab.shape[0] != M \
+            or T * Nbase != Rn or tuple(pairs.shape) != (Nbase, 2) \
+            or (weights is not None and tuple(weights.shape) != (Rn,)):
+        raise ValueError("cohs [M, R, 2, 2], chunk_tab [M, T], pairs "
+                         "[Nbase, 2] and weights [R] with T * Nbase rows")
+    dev = cohs.device
+    pr = pairs.to(device=dev, dtype=torch.long)
+    live = (pr >= 0).all(dim=1).repeat(T)
+    bb = pr.clamp_min(0).repeat(T, 1)
+    Jd = J.to(torch.complex128)
+    wt = None if weights is None else weights.to(device=dev,
+                                                 dtype=torch.float64)
+    JtJ = torch.zeros(Mt, 8 * N, 8 * N, dtype=torch.float64, device=dev)
+    for ci in range(M):
+        ct = chunk_tab[ci].to(device=dev, dtype=torch.long)
+        cs, slot = torch.unique(ct, return_inverse=True)
+        C = cohs[ci].to(torch.complex128)
+        C = torch.where(live[:, None, None], C, C.new_zeros(()))
+        JtJ[cs] += R.jtj_jtr(C, C, Jd[cs], bb, N, wt,
+                             slot.repeat_interleave(Nbase), len(cs))[0]
+    return JtJ
+
+
 def diffuse_kernel_on():
     """SAGECAL_DIFFUSE_KERNEL=1 opts ConsensusADMM.diffuse_coherencies, the
     diffuse hook of sagecal-mpi -D, into the kernels of diffuse.hip on device

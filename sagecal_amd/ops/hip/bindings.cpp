@@ -1027,6 +1027,56 @@ torch::Tensor leverage_rows(
   return lev;
 }
 
+// The float64 normal matrices of every chunk (normal_f64.hip): cohs
+// [M, R, 4] and J [Mt, N, 4] complex64, optional wts [R] float32, chunk_tab
+// [M, T] and pairs [Nbase, 2] int32 with R == T * Nbase; pieces [E, 4] and
+// piece_off [Mt + 1] int32 from hip_host._lbfgs_extents, pidx [N, N] int32
+// from hip_host._normal_pair_index, sta_off [N + 1] and sta_ent int32 from
+// hip_host._lbfgs_stations. Returns JtJ [Mt, 8N, 8N] float64. The caller
+// guarantees chunk ids below Mt, pair entries below N and tables built from
+// these pairs and this chunk_tab.
+torch::Tensor normal_matrices(
+    torch::Tensor cohs, torch::Tensor J, c10::optional<torch::Tensor> wts,
+    torch::Tensor chunk_tab, torch::Tensor pairs, torch::Tensor pieces,
+    torch::Tensor piece_off, torch::Tensor pidx, torch::Tensor sta_off,
+    torch::Tensor sta_ent) {
+  const torch::Device dev = cohs.device();
+  TORCH_CHECK(on_dev(cohs, dev, torch::kComplexFloat) && cohs.dim() == 3 &&
+              cohs.size(0) >= 1 && cohs.size(1) >= 1 && cohs.size(2) == 4,
+              "cohs must be contiguous [M, R, 4] complex64 on the device");
+  const int64_t M = cohs.size(0), R = cohs.size(1);
+  check_solution_tables(J, chunk_tab, pairs, M, R, dev);
+  const int64_t Mt = J.size(0), N = J.size(1), Nbase = pairs.size(0);
+  TORCH_CHECK(!wts.has_value() || on_dev(*wts, dev, torch::kFloat, R),
+              "weights must be contiguous [R] float32");
+  TORCH_CHECK(on_dev(pieces, dev, torch::kInt) && pieces.dim() == 2 &&
+              pieces.size(0) >= 1 && pieces.size(0) <= 65535 &&
+              pieces.size(1) == 4,
+              "pieces must be contiguous [E, 4] int32, E <= 65535");
+  TORCH_CHECK(Mt <= 65535 && N <= 8192, "at most 65535 chunks, 8192 stations");
+  TORCH_CHECK(on_dev(piece_off, dev, torch::kInt, Mt + 1) &&
+              on_dev(pidx, dev, torch::kInt, N * N) &&
+              on_dev(sta_off, dev, torch::kInt, N + 1) &&
+              on_dev(sta_ent, dev, torch::kInt) &&
+              sta_ent.numel() <= 2 * Nbase,
+              "piece_off [Mt + 1], pidx [N, N], sta_off [N + 1] and sta_ent "
+              "must be contiguous int32 on the device");
+  check_aligned16({&cohs, &J, &pieces}, "cohs, J and pieces");
+  NormalF64Args a = {};
+  a.cohs = ccptr(cohs); a.J = ccptr(J);
+  a.wts = wts.has_value() ? fp(*wts) : nullptr;
+  a.pairs = ip(pairs); a.pieces = ip(pieces); a.piece_off = ip(piece_off);
+  a.pidx = ip(pidx); a.sta_off = ip(sta_off); a.sta_ent = ip(sta_ent);
+  a.M = (int)M; a.T = (int)chunk_tab.size(1); a.Nbase = (int)Nbase;
+  a.N = (int)N; a.Mt = (int)Mt; a.E = (int)pieces.size(0);
+  const auto f64 = torch::dtype(torch::kDouble).device(dev);
+  auto part = torch::empty({pieces.size(0), Nbase, NORMAL_F64_NV}, f64);
+  auto JtJ = torch::empty({Mt, 8 * N, 8 * N}, f64);
+  CHECK_HIP(launch_normal_f64(a, part.data_ptr<double>(),
+                              JtJ.data_ptr<double>(), cur_stream()));
+  return JtJ;
+}
+
 // Doubles of scratch spd_inverse needs for Mt matrices of n: W [Mt, n, n] and
 // the inverted diagonal blocks [Mt, ceil(n / 32), 2, 32, 32].
 static int64_t spd_inverse_scratch(int64_t Mt, int64_t n) {
@@ -1158,6 +1208,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "influence-map leverage, all clusters in one launch (gfx950)",
         py::arg("cohs"), py::arg("J"), py::arg("Hinv"), py::arg("wts"),
         py::arg("chunk_tab"), py::arg("pairs"), py::arg("pieces"));
+  m.def("normal_matrices", &normal_matrices,
+        "float64 normal matrices of every chunk, two launches (gfx950)",
+        py::arg("cohs"), py::arg("J"), py::arg("wts"), py::arg("chunk_tab"),
+        py::arg("pairs"), py::arg("pieces"), py::arg("piece_off"),
+        py::arg("pidx"), py::arg("sta_off"), py::arg("sta_ent"));
   m.def("rtr_tcg", &rtr_tcg, "RTR truncated-CG inner solve (gfx950)",
         py::arg("JtJ"), py::arg("Jtr"), py::arg("J"), py::arg("iw"),
         py::arg("delta"), py::arg("maxit"), py::arg("kappa"));

@@ -181,6 +181,28 @@ struct LeverageArgs {
   int M, T, Nbase, N, Mt, E;
 };
 
+// The float64 normal matrices of the influence map (normal_f64.hip). Rows
+// r = t*Nbase + b, R = T*Nbase. The host guarantees pair entries below N,
+// chunk ids in 0..Mt-1, pieces and piece_off as hip_host._lbfgs_extents
+// builds them (sorted by chunk), sta_off and sta_ent as
+// hip_host._lbfgs_stations does, and pidx from hip_host._normal_pair_index.
+// cohs, J and pieces 16-byte aligned.
+struct NormalF64Args {
+  const float2* cohs;       // [M, R, 4] coherencies
+  const float2* J;          // [Mt, N, 4] packed solutions
+  const float* wts;         // [R] row weights, or null
+  const int* pairs;         // [Nbase, 2]; a negative entry: the pair adds
+                            // nothing
+  const int* pieces;        // [E, 4] (ci, c, t0, t1): timeslots t0 <= t < t1
+                            // of cluster ci, all of global chunk c
+  const int* piece_off;     // [Mt + 1] first piece of each chunk
+  const int* pidx;          // [N, N]: 2 b for pair b stored as (row, col),
+                            // 2 b + 1 as (col, row), -1 for none
+  const int* sta_off;       // [N + 1] a station's entries in sta_ent
+  const int* sta_ent;       // 2 b + side, by station, then by entry
+  int M, T, Nbase, N, Mt, E;
+};
+
 // The float64 inverse of damped SPD matrices (spd_inverse.hip), n a multiple
 // of 8 and nt = ceil(n / 32) blocks a side. All pointers 16-byte aligned.
 struct SpdInverseArgs {
@@ -246,6 +268,18 @@ hipError_t launch_spd_inverse(SpdInverseArgs a, double* X,
 // timeslot). hipErrorInvalidValue: a dimension < 1, a null table, E > 65535
 // or R * M beyond 2^40.
 hipError_t launch_leverage(LeverageArgs a, double* lev, hipStream_t stream);
+
+// Threads per workgroup of k_normal_accum (WAVE pairs) and k_normal_expand
+// (a tile of 8 x 8 stations).
+#define NORMAL_F64_TB 256
+// Doubles per (piece, pair) of the scratch of launch_normal_f64.
+#define NORMAL_F64_NV 40
+// JtJ [Mt, 8N, 8N] float64, fully written, blocks of absent pairs and of
+// chunks without a piece zero. Scratch part [E, Nbase, NORMAL_F64_NV],
+// contents unspecified on entry and exit. hipErrorInvalidValue: a dimension
+// < 1, a null table, E or Mt > 65535, N > 8192 or R * M beyond 2^40.
+hipError_t launch_normal_f64(NormalF64Args a, double* part, double* JtJ,
+                             hipStream_t stream);
 
 // Threads per workgroup of k_rtr_tcg and the most parameters of a chunk:
 // a thread owns one float4 of every vector.

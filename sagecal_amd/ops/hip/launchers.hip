@@ -10,6 +10,7 @@
 #include "joint_jtj.hip"
 #include "rtr_tcg.hip"
 #include "leverage.hip"
+#include "normal_f64.hip"
 #include "spd_inverse.hip"
 #include "diffuse.hip"
 #include "cholesky.hip"
@@ -316,6 +317,25 @@ hipError_t launch_leverage(LeverageArgs a, double* lev, hipStream_t stream) {
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_leverage, dim3((a.Nbase + WAVE - 1) / WAVE, a.E),
                      dim3(LEVERAGE_TB), 0, stream, a, lev);
+  return hipGetLastError();
+}
+
+// one workgroup per (tile of WAVE pairs, piece), then one per (tile pair of
+// 8 x 8 stations, chunk); static LDS (normal_f64.hip)
+hipError_t launch_normal_f64(NormalF64Args a, double* part, double* JtJ,
+                             hipStream_t stream) {
+  if (a.M < 1 || a.T < 1 || a.Nbase < 1 || a.N < 1 || a.N > 8192 ||
+      a.Mt < 1 || a.Mt > 65535 || a.E < 1 || a.E > 65535 ||
+      a.cohs == nullptr || a.J == nullptr || a.pairs == nullptr ||
+      a.pieces == nullptr || a.piece_off == nullptr || a.pidx == nullptr ||
+      a.sta_off == nullptr || a.sta_ent == nullptr || part == nullptr ||
+      JtJ == nullptr || (long long)a.T * a.Nbase * a.M > (1LL << 40))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_normal_accum, dim3((a.Nbase + WAVE - 1) / WAVE, a.E),
+                     dim3(NORMAL_F64_TB), 0, stream, a, part);
+  const int nt = (a.N + 7) / 8;
+  hipLaunchKernelGGL(k_normal_expand, dim3(nt * (nt + 1) / 2, a.Mt),
+                     dim3(NORMAL_F64_TB), 0, stream, a, part, JtJ);
   return hipGetLastError();
 }
 

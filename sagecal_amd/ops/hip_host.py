@@ -1279,6 +1279,86 @@ def leverage_rows(cohs, J, Hinv, chunk_tab, pairs, weights=None):
         None if weights is None else f64(weights), chunk_tab, pairs, pieces)
 
 
+NORMAL_TSPLIT = 64    # most timeslots of one piece of k_normal_accum
+
+
+def _normal_pair_index(pairs, N):
+    """pidx [N, N] int32 on pairs' device for k_normal_expand: 2 b at (p, q)
+    and 2 b + 1 at (q, p) for every pair b = (p, q) without a negative entry,
+    -1 elsewhere. A cross block belongs to one pair, so a pair named twice,
+    either way round, or a pair of a station with itself raises ValueError.
+    Reads the table back, so it is built once per table."""
+    def build():
+        pr = pairs.cpu().numpy()
+        ok = np.flatnonzero((pr >= 0).all(axis=1))
+        p, q = pr[ok, 0], pr[ok, 1]
+        key = np.minimum(p, q).astype(np.int64) * N + np.maximum(p, q)
+        if (p == q).any() or len(np.unique(key)) != len(key):
+            raise ValueError("the float64 normal matrices need every pair "
+                             "once and of two stations")
+        idx = np.full((N, N), -1, dtype=np.int32)
+        idx[p, q] = 2 * ok
+        idx[q, p] = 2 * ok + 1
+        return torch.from_numpy(idx).to(pairs.device)
+    return _table_memo('pidx', pairs, (N,), build)
+
+
+def normal_matrices(cohs, J, chunk_tab, pairs, weights=None):
+    """The Gauss-Newton normal matrices JtJ [Mt, 8N, 8N] float64 of every
+    chunk of every cluster in the two launches of normal_f64.hip: cohs
+    [M, R, 2, 2] and J [Mt, N, 2, 2] complex, read as complex64, chunk_tab
+    [M, T] global chunk id of each (cluster, timeslot), pairs [Nbase, 2] in
+    any order and either way round, each pair at most once, R = T * Nbase,
+    weights [R] (read as float32) or None. Every product and sum is float64;
+    a pair with a negative entry adds nothing, blocks of pairs that do not
+    occur and chunks that chunk_tab does not name are zero. JtJ == JtJ^T to
+    the bit, and bitwise the same from call to call and in any batch. The
+    first call with a new pair or chunk table reads it back, for the bounds
+    check and the index tables; after that the path has no host
+    synchronisation."""
+    dev = cohs.device
+    if cohs.dim() != 4 or tuple(cohs.shape[2:]) != (2, 2):
+        raise ValueError(f"cohs must be [M, R, 2, 2], got {tuple(cohs.shape)}")
+    M, R = int(cohs.shape[0]), int(cohs.shape[1])
+    if J.dim() != 4 or tuple(J.shape[2:]) != (2, 2) or J.shape[0] < 1 \
+            or J.shape[1] < 1:
+        raise ValueError("J must be [Mt, N, 2, 2]")
+    Mt, N = int(J.shape[0]), int(J.shape[1])
+    if chunk_tab.dim() != 2 or chunk_tab.shape[0] != M:
+        raise ValueError(f"chunk_tab must be [{M}, T]")
+    if pairs.dim() != 2 or pairs.shape[1] != 2 \
+            or chunk_tab.shape[1] * pairs.shape[0] != R:
+        raise ValueError("pairs must be [Nbase, 2] with T * Nbase rows")
+    if weights is not None and tuple(weights.shape) != (R,):
+        raise ValueError(f"weights must be [{R}]")
+    zeros = lambda: torch.zeros(Mt, 8 * N, 8 * N, dtype=torch.float64,
+                                device=dev)
+    if M == 0 or R == 0:
+        return zeros()
+    i32 = lambda t: t.to(device=dev, dtype=torch.int32).contiguous()
+    chunk_tab, pairs = i32(chunk_tab), i32(pairs)
+    # the kernels index J and JtJ by both tables with no checks of their own
+    if _pair_range(pairs)[1] >= N:
+        raise ValueError(f"pairs name a station outside the {N} of J")
+    lo, hi = _pair_range(chunk_tab)
+    if lo < 0 or hi >= Mt:
+        raise ValueError(f"chunk_tab names chunks {lo}..{hi}, J has {Mt}")
+    pieces, piece_off = _lbfgs_extents(chunk_tab, Mt, NORMAL_TSPLIT)
+    pidx = _normal_pair_index(pairs, N)
+    sta_off, sta_ent = _lbfgs_stations(pairs, N)
+    if sta_ent.numel() == 0:                 # every pair flagged
+        return zeros()
+
+    def c64(t, *shape):
+        t = t.to(torch.complex64).reshape(*shape).contiguous()
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+    if weights is not None:
+        weights = weights.to(device=dev, dtype=torch.float32).contiguous()
+    return _ext().normal_matrices(
+        c64(cohs, M, R, 4), c64(J, Mt, N, 4), weights, chunk_tab, pairs,
+        pieces, piece_off, pidx, sta_off, sta_ent)
+
+
 _spd_scratch = {}
 
 

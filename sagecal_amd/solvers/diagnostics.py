@@ -48,20 +48,26 @@ def leverage(x, coh, J, bb, N, weights=None, chunk_rows=None, nchunk=1,
     """Per-baseline leverage scores [B] for one cluster's solve. With T and
     Nbase, B == T * Nbase structured rows (r = t*Nbase + b, pairs bb[:Nbase],
     one chunk per timeslot) and x on the device, the rows go through
-    ops.leverage_rows and no per-row matrix is formed."""
-    JtJ, Jtr, _ = ops.jtj_jtr(x, coh, J, bb, N, weights, chunk_rows,
-                              nchunk, layout)
+    ops.leverage_rows and no per-row matrix is formed; with
+    SAGECAL_NORMAL_F64=1 the normal matrix of such rows is the float64 one
+    of ops.normal_matrices, not the float32 one of ops.jtj_jtr."""
     dev = x.device
-    Hinv = _damped_inverse(JtJ, mu)
-    if T is not None and Nbase is not None and x.is_cuda \
-            and x.shape[0] == T * Nbase:
+    structured = T is not None and Nbase is not None and x.is_cuda \
+        and x.shape[0] == T * Nbase
+    if structured:
         if chunk_rows is None:
             tab = torch.zeros(1, T, dtype=torch.int32, device=dev)
         else:
             tab = chunk_rows[::Nbase].to(torch.int32)[None]
-        return ops.leverage_rows(coh[None], J, Hinv, tab,
-                                 ops.lbfgs_pair_table(bb, Nbase, dev),
-                                 weights)[0]
+        pairs = ops.lbfgs_pair_table(bb, Nbase, dev)
+    if structured and ops.normal_f64_on():
+        JtJ = ops.normal_matrices(coh[None], J, tab, pairs, weights)
+    else:
+        JtJ = ops.jtj_jtr(x, coh, J, bb, N, weights, chunk_rows, nchunk,
+                          layout)[0]
+    Hinv = _damped_inverse(JtJ, mu)
+    if structured:
+        return ops.leverage_rows(coh[None], J, Hinv, tab, pairs, weights)[0]
     if chunk_rows is None:
         chunk_rows = torch.zeros(x.shape[0], dtype=torch.long, device=dev)
     # per-baseline design blocks (as in reference.jtj_jtr derivation)
@@ -128,7 +134,8 @@ def influence_map(state, cohs, tile, bb, cluster=0, layout=None):
     """Replace-output-data diagnostics (-i 1): per-visibility leverage of
     the chosen cluster's solve, shaped like the data [B]. cluster=None: the
     leverage of every cluster [M, B], from one batched inverse over all
-    chunks and one ops.leverage_rows call."""
+    chunks and one ops.leverage_rows call; with SAGECAL_NORMAL_F64=1 on the
+    device also from one float64 assembly, ops.normal_matrices."""
     T, Nbase = tile.tilesz, tile.Nbase
     Bn = tile.x.shape[0]
     dev = tile.x.device
@@ -146,11 +153,14 @@ def influence_map(state, cohs, tile, bb, cluster=0, layout=None):
     if Bn != T * Nbase:
         raise ValueError(f"cluster=None needs T * Nbase = {T * Nbase} rows, "
                          f"got {Bn}")
-    JtJ = torch.cat([
-        ops.jtj_jtr(tile.x, cohs[ci], state.cluster_J(ci), bb, state.N,
-                    None, rows(ci), state.nchunks[ci], layout)[0]
-        for ci in range(state.M)])
-    return ops.leverage_rows(
-        cohs, state.J, _damped_inverse(JtJ, 1e-6),
-        ops.lbfgs_chunk_table(state.chunk_off, state.nchunks, T, dev),
-        ops.lbfgs_pair_table(bb, Nbase, dev))
+    tab = ops.lbfgs_chunk_table(state.chunk_off, state.nchunks, T, dev)
+    pairs = ops.lbfgs_pair_table(bb, Nbase, dev)
+    if tile.x.is_cuda and ops.normal_f64_on():
+        JtJ = ops.normal_matrices(cohs, state.J, tab, pairs)
+    else:
+        JtJ = torch.cat([
+            ops.jtj_jtr(tile.x, cohs[ci], state.cluster_J(ci), bb, state.N,
+                        None, rows(ci), state.nchunks[ci], layout)[0]
+            for ci in range(state.M)])
+    return ops.leverage_rows(cohs, state.J, _damped_inverse(JtJ, 1e-6), tab,
+                             pairs)

@@ -22,7 +22,16 @@ of 512 from the float32 JtJ, and in shape (c), the 10 matrices of one chunk
 per cluster; at mu = 1e-6 as the diagnostic sets it and at 1e-2, with the
 number of matrices the kernels flag as not positive definite (their last
 kernel skips those, and the diagnostic sends them to torch.linalg.inv), and
-influence_map(cluster=None) with SAGECAL_INVERSE_KERNEL=1 and without."""
+influence_map(cluster=None) with SAGECAL_INVERSE_KERNEL=1 and without.
+
+    python tools/bench_leverage.py --sections d_normal_f64 \
+        --out profiles/normal_f64.json
+
+times the float64 assembly of normal_f64.hip (ops.normal_matrices) in shape
+(b) against the ten float32 ops.jtj_jtr calls it replaces, counts the
+matrices the inverse kernels flag for either, and times the whole map with
+SAGECAL_NORMAL_F64=1 and SAGECAL_INVERSE_KERNEL=1, the latter alone, and
+neither."""
 import argparse
 import json
 import os
@@ -200,6 +209,71 @@ def shape_c(args):
     return out
 
 
+def with_env(fn, *names):
+    def run():
+        os.environ.update({n: '1' for n in names})
+        try:
+            return fn()
+        finally:
+            for n in names:
+                os.environ.pop(n)
+    return run
+
+
+def shape_d(args):
+    """Shape (b) again for the float64 assembly of normal_f64.hip:
+    ops.normal_matrices against the ten ops.jtj_jtr calls, what the inverse
+    kernels flag for either matrix at mu = 1e-6, and the whole map with
+    SAGECAL_NORMAL_F64=1 and SAGECAL_INVERSE_KERNEL=1, the latter alone, and
+    neither."""
+    T, M, K = 960, 10, 16
+    state, cohs, tile, bb = make(T, [K] * M)
+    Nbase, Rn = tile.Nbase, T * tile.Nbase
+    lay = hip_host.BaselineLayout(bb, Nbase, T, 1, N, DEV)
+    rows = R.chunk_rows_for(0, state.nchunks, T, Nbase, Rn, DEV)
+    tab = ops.lbfgs_chunk_table(state.chunk_off, state.nchunks, T, DEV)
+    pairs = ops.lbfgs_pair_table(bb, Nbase, DEV)
+
+    def assemble32():
+        return torch.cat([
+            ops.jtj_jtr(tile.x, cohs[ci], state.cluster_J(ci), bb, N, None,
+                        rows, K, lay)[0] for ci in range(M)])
+    assemble64 = lambda: ops.normal_matrices(cohs, state.J, tab, pairs)
+    imap = lambda: diag.influence_map(state, cohs, tile, bb, cluster=None,
+                                      layout=lay)
+    maps = {'influence_map_normal_f64_and_inverse_kernels': with_env(
+                imap, 'SAGECAL_NORMAL_F64', 'SAGECAL_INVERSE_KERNEL'),
+            'influence_map_inverse_kernels': with_env(
+                imap, 'SAGECAL_INVERSE_KERNEL'),
+            'influence_map_neither': imap}
+    out = compare({'jtj_assembly_ten_calls_float32': assemble32,
+                   'normal_matrices_float64': assemble64, **maps},
+                  args.warmup, args.runs)
+    J32, J64 = assemble32(), assemble64()
+    flagged = lambda A: int(hip_host.spd_inverse_damped(
+        A, 1e-6, return_info=True)[1].count_nonzero())
+    out['kernels_flag_not_positive_definite_mu1e-06'] = {
+        'float32_assembly': flagged(J32), 'float64_assembly': flagged(J64)}
+    out['max_abs_float32_minus_float64_assembly'] = float(
+        (J32 - J64).abs().max())
+    out['max_abs_assembly'] = float(J64.abs().max())
+    del J32, J64
+    levs = {k: fn() for k, fn in maps.items()}
+    names = list(levs)
+    out['max_abs_diff_of_maps'] = {
+        f'{a} vs {b}': float((levs[a] - levs[b]).abs().max())
+        for i, a in enumerate(names) for b in names[i + 1:]}
+    # coh in, the 40 doubles per (pair, piece) out and in again, JtJ out
+    pieces = M * K * -(-(T // K) // hip_host.NORMAL_TSPLIT)
+    nbytes = (M * Rn * 32 + 2 * pieces * Nbase * 40 * 8
+              + M * K * (8 * N) ** 2 * 8)
+    ms = out['normal_matrices_float64']['ms_median']
+    out.update(rows=Rn, clusters=M, chunks=M * K,
+               bytes_normal_matrices_must_move=nbytes,
+               achieved_GB_per_s=round(nbytes / ms / 1e6, 1))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default='profiles/leverage.json')
@@ -213,7 +287,8 @@ def main():
            'repeated', 'device': 'MI355X (gfx950)', 'N': N}
     for name, fn in (('a_one_cluster_T8', shape_a),
                      ('b_bench_default', shape_b),
-                     ('c_ten_chunks', shape_c)):
+                     ('c_ten_chunks', shape_c),
+                     ('d_normal_f64', shape_d)):
         if name not in args.sections.split(','):
             continue
         res[name] = fn(args)
